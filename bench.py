@@ -19,7 +19,16 @@ basis that contains the README champion), `feature_linear`, and
 `random_linear` (exactly `_create_random_policy`,
 `funsearch/funsearch_integration.py:403-431`).
 
+A plain run times the generations and prints the result line.  `--full` adds,
+after the timed region, the program-path measurements (`program_path`: FunSearch
+candidate programs through the native backend, against the CPU VM) and the
+device-math self-check (`device_math`).  `--dump-outputs DIR` writes what the
+last timed generation returned (every island's result table and the candidates
+it belongs to) as .npy files; with the same arguments two runs write the same
+arrays.
+
     python bench.py --gpus 1 --steps 10 --warmup 2
+    python bench.py --gpus 1 --steps 10 --warmup 2 --full
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \\
         --master-port 29500 bench.py --gpus 8 --steps 10 --warmup 2
 """
@@ -38,6 +47,28 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 BASELINE_EVALS_PER_S = 15.84   # reference eval path, 8 CPU workers
 BASELINE_SYNTHETIC_EVALS_PER_S = 0.1   # config 5: ~10 s per reference eval on 1 CPU core
+
+
+DUMP_BUDGET_BYTES = 64 << 20   # --dump-outputs: all files of a run together stay below this
+
+
+def dump_outputs(out_dir: str, last_out: dict, rank: int, seed: int, world_size: int = 1) -> None:
+    """--dump-outputs: what the last timed generation returned, per island, as float64 .npy files:
+    ``table_r<rank>_i<island>.npy`` ([P, 13] result table, engine.RESULT_COLUMNS order) and
+    ``weights_r<rank>_i<island>.npy`` ([P, K] candidates it was computed from, same row order).
+    Above the size budget every array keeps the same seeded sample of rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(w.nbytes + t.nbytes for _, w, t in last_out.values())
+    budget = DUMP_BUDGET_BYTES // max(1, world_size)
+    for li in sorted(last_out):
+        _, w, tab = last_out[li]
+        w = np.asarray(w, dtype=np.float64)
+        if total > budget:
+            keep = max(1, int(len(tab) * budget / total * 0.98))
+            rows = np.sort(np.random.default_rng(seed).choice(len(tab), keep, replace=False))
+            w, tab = w[rows], tab[rows]
+        np.save(os.path.join(out_dir, f"table_r{rank}_i{li}.npy"), tab)
+        np.save(os.path.join(out_dir, f"weights_r{rank}_i{li}.npy"), w)
 
 
 def main() -> None:
@@ -95,6 +126,13 @@ def main() -> None:
     ap.add_argument("--time-budget", type=float, default=0.0,
                     help="run generations until this many seconds have passed (instead of --steps); "
                          "steps = generations completed")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps: write every island's last-generation result table "
+                         "(and the weights it was computed from) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need, after the timed region: the program-path "
+                         "measurements (--programs, --novel, --novel-large, --evolved, --evolved-service-s) and the "
+                         "device-math self-check")
     args = ap.parse_args()
 
     from funsearch_kubernetes_simulator_amd.parallel import dist
@@ -148,8 +186,11 @@ def main() -> None:
 
     best_row = [None, -1.0, None, -1]   # table row, score, weights, generation
     events = [0.0]
+    last_out = {}                       # island -> (generation, weights, result table): --dump-outputs
 
-    def absorb(isl, props, tab, gen: int) -> None:
+    def absorb(isl, props, tab, gen: int, li: int = 0) -> None:
+        if args.dump_outputs and (args.time_budget > 0 or gen == args.warmup + args.steps - 1):
+            last_out[li] = (gen, props.copy(), np.array(tab, dtype=np.float64))
         sc = tab[:, COLS["score"]]
         isl.update(props, sc, tab[:, COLS["n_events"]])
         events[0] += float(tab[:, COLS["n_events"]].sum())
@@ -163,62 +204,82 @@ def main() -> None:
             props = [propose(isl) for isl in islands]
             tab = ev.evaluate_family(args.family, np.concatenate(props))
             off = 0
-            for isl, p in zip(islands, props):
-                absorb(isl, p, tab[off:off + len(p)], gen)
+            for li, (isl, p) in enumerate(zip(islands, props)):
+                absorb(isl, p, tab[off:off + len(p)], gen, li)
                 off += len(p)
 
     def run_async(g0: int, count: int) -> None:
         """`count` generations of every island, back to back on each island's
         own slot: no island waits for another, at migration points included
         (an epoch barrier idled the chip while the last island finished its
-        epoch).  When the slowest local island has passed a boundary (a
-        multiple of --migrate-every) the rank's current elites go into a
-        non-blocking all-gather -- issued in boundary order, so every rank
-        issues the same sequence -- and each island takes its ring
-        predecessor's migrants from the newest completed gather when it next
-        reaches a boundary (islands that finish first take it at the end)."""
+        epoch).  Migration does not depend on which island finishes when, so
+        a run repeats generation for generation: an island that reaches a
+        boundary (a multiple of --migrate-every) records its elites as they
+        are then; when the slowest local island has recorded, the rank's
+        records go into a non-blocking all-gather -- issued in boundary
+        order, so every rank issues the same sequence -- and each island
+        takes its ring predecessor's migrants of one boundary when it reaches
+        the next one (those of the last boundary at the end).  An island
+        waits only when it is a whole epoch ahead of the slowest one."""
         M = args.migrate_every
         k = len(islands)
         props, gens, left = [None] * k, [g0] * k, [count] * k
         bounds = [b for b in range(g0 + 1, g0 + count + 1) if M and b % M == 0]
-        issued, gathers, newest, taken = 0, [], None, [-1] * k
+        snaps = [[None] * k for _ in bounds]      # per boundary: every island's migrants at that generation
+        gathered = [None] * len(bounds)           # per boundary: the completed all-gather
+        gathers, taken, owed = [], [-1] * k, [-1] * k
 
         def launch(i: int) -> None:
             props[i] = propose(islands[i])
             ev.submit_family(i, args.family, props[i])
 
+        def take(i: int) -> bool:
+            """Island i takes the gathers it is owed, in boundary order (False: one is still under way)."""
+            while taken[i] < owed[i]:
+                if gathered[taken[i] + 1] is None:
+                    return False
+                taken[i] += 1
+                inject_one(islands, i, gathered[taken[i]], ctx.rank)
+            return True
+
         for i in range(k):
             launch(i)
-        pending = set(range(k))
+        pending, held = set(range(k)), set()
         while pending or gathers:
             progressed = False
-            while issued < len(bounds) and min(gens) >= bounds[issued]:
-                gathers.append((issued, dist.all_gather_array_async(migration_records(islands, args.migrants))))
-                issued += 1
             while gathers and gathers[0][1].done():
-                newest = (gathers[0][0], gathers[0][1].wait())
+                gathered[gathers[0][0]] = gathers[0][1].wait()
                 gathers.pop(0)
                 progressed = True
-            for i in sorted(pending):
+            for i in sorted(held):
+                if take(i):
+                    held.discard(i)
+                    launch(i)
+                    progressed = True
+            for i in sorted(pending - held):
                 if not ev.ready(i):
                     continue
-                absorb(islands[i], props[i], ev.wait(i), gens[i])
+                absorb(islands[i], props[i], ev.wait(i), gens[i], i)
                 gens[i] += 1
                 left[i] -= 1
                 progressed = True
-                if M and gens[i] % M == 0 and newest is not None and taken[i] < newest[0]:
-                    inject_one(islands, i, newest[1], ctx.rank)
-                    taken[i] = newest[0]
-                if left[i]:
+                if M and gens[i] % M == 0:
+                    bi = bounds.index(gens[i])
+                    snaps[bi][i] = islands[i].migrants(args.migrants)
+                    if all(s is not None for s in snaps[bi]):
+                        gathers.append((bi, dist.all_gather_array_async(np.stack(snaps[bi]))))
+                    owed[i] = bi - 1
+                if not left[i]:
+                    pending.discard(i)
+                elif take(i):
                     launch(i)
                 else:
-                    pending.discard(i)
+                    held.add(i)
             if not progressed:
                 time.sleep(0.0002)
-        if newest is not None:
-            for i in range(k):
-                if taken[i] < newest[0]:
-                    inject_one(islands, i, newest[1], ctx.rank)
+        for i in range(k):
+            owed[i] = len(bounds) - 1
+            take(i)
 
     def run(g0: int, count: int) -> None:
         """`count` generations of every island; migration at every multiple of
@@ -262,8 +323,14 @@ def main() -> None:
     elapsed = dist.all_reduce_max(time.perf_counter() - t0)
     events_total = dist.all_reduce_sum(events[0])
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_out, ctx.rank, args.seed, ctx.world_size)
+
     program_path = None
     jit_init_s = None
+    if not args.full:
+        # a plain run measures the headline figure alone
+        args.programs = args.novel = args.novel_large = args.evolved = 0
     if ev.device is not None and (args.programs > 0 or args.novel > 0 or args.novel_large > 0 or args.evolved > 0):
         # first-use JIT initialisation, reported on its own (not in the first batch's jit_s)
         jit_init_s = round(ev.device.warm_native(), 3)
@@ -348,7 +415,7 @@ def main() -> None:
             "program_path": program_path,
             "program_path_jit_init_s": jit_init_s,
         }
-        if ev.device is not None:
+        if ev.device is not None and args.full:
             from funsearch_kubernetes_simulator_amd.ops.hip_engine import math_selfcheck_info
             out["device_math"] = math_selfcheck_info()
         if args.time_budget > 0:

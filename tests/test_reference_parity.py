@@ -1,23 +1,27 @@
 """Differential test against the reference implementation itself.
 
-Runs the reference's own simulator (read-only checkout, imported with a
-3-line ``enum.StrEnum`` shim for Python 3.10) on random sub-traces and random
-policies in a subprocess, and compares its scores with the native engine.
-Skipped when the reference checkout is not mounted (e.g. on the GPU box).
+The reference's own simulator was run on random sub-traces and random
+policies; the scores it returned are stored in
+``tests/golden/reference_parity_scores.json`` and the native engine must
+reproduce them bit for bit.  The file holds each case (the sub-trace's first
+pod and length, the policy program this project generated) next to the score
+the reference gave it.
+
+    python tests/test_reference_parity.py <reference checkout>
+
+records the file again: it runs the reference (imported with a 3-line
+``enum.StrEnum`` shim for Python 3.10) in a subprocess on the same cases.
 """
 import json
 import os
 import subprocess
 import sys
+import tempfile
 
 import numpy as np
 import pytest
 
-from funsearch_kubernetes_simulator_amd.core import load_default_workload
-from funsearch_kubernetes_simulator_amd.engine import Evaluator
-from funsearch_kubernetes_simulator_amd.models import families as fam
-
-REF = "/root/reference"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_parity_scores.json")
 
 DRIVER = r'''
 import enum, json, sys, copy
@@ -55,10 +59,8 @@ print(json.dumps(out))
 '''
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not mounted")
-@pytest.mark.slow
-def test_random_subtraces_random_policies_match_reference(tmp_path):
-    w = load_default_workload()
+def _cases(w):
+    from funsearch_kubernetes_simulator_amd.models import families as fam
     rng = np.random.default_rng(2024)
     cases = []
     for k in range(8):
@@ -68,15 +70,43 @@ def test_random_subtraces_random_policies_match_reference(tmp_path):
         family = "random_linear" if k % 2 else "feature_linear"
         W = (fam.sample_random_linear if family == "random_linear" else fam.sample_feature_linear)(1, rng)[0]
         cases.append({"pods": [w.pods.pod_ids[i] for i in idx], "code": fam.to_program(family, W), "idx": idx})
-    job = tmp_path / "job.json"
-    job.write_text(json.dumps([{"pods": c["pods"], "code": c["code"]} for c in cases]))
-    drv = tmp_path / "drv.py"
-    drv.write_text(DRIVER)
-    r = subprocess.run([sys.executable, str(drv), REF, str(job)], capture_output=True, text=True, timeout=900)
+    return cases
+
+
+def _record(ref: str) -> None:
+    from funsearch_kubernetes_simulator_amd.core import load_default_workload
+    cases = _cases(load_default_workload())
+    with tempfile.TemporaryDirectory() as tmp:
+        job, drv = os.path.join(tmp, "job.json"), os.path.join(tmp, "drv.py")
+        with open(job, "w") as f:
+            json.dump([{"pods": c["pods"], "code": c["code"]} for c in cases], f)
+        with open(drv, "w") as f:
+            f.write(DRIVER)
+        r = subprocess.run([sys.executable, drv, ref, job], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
-    ref_scores = json.loads(r.stdout.strip().splitlines()[-1])
+    scores = json.loads(r.stdout.strip().splitlines()[-1])
+    with open(GOLDEN, "w") as f:
+        json.dump({"seed": 2024,
+                   "cases": [{"start": int(c["idx"][0]), "n_pods": len(c["idx"]), "code": c["code"],
+                              "score": repr(float(s))} for c, s in zip(cases, scores)]}, f, indent=1)
+        f.write("\n")
+
+
+@pytest.mark.slow
+def test_random_subtraces_random_policies_match_reference():
+    from funsearch_kubernetes_simulator_amd.core import load_default_workload
     from funsearch_kubernetes_simulator_amd.core.arrays import Workload
-    for c, ref in zip(cases, ref_scores):
-        sub = Workload(w.cluster, w.pods.subset(c["idx"]))
-        got = Evaluator(sub, device="cpu").scores([c["code"]])[0]
-        assert got == ref, (got, ref)
+    from funsearch_kubernetes_simulator_amd.engine import Evaluator
+    w = load_default_workload()
+    with open(GOLDEN) as f:
+        golden = json.load(f)["cases"]
+    assert len(golden) == 8
+    for g in golden:
+        sub = Workload(w.cluster, w.pods.subset(np.arange(g["start"], g["start"] + g["n_pods"])))
+        got = Evaluator(sub, device="cpu").scores([g["code"]])[0]
+        assert got == float(g["score"]), (got, g["score"])
+
+
+if __name__ == "__main__":
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    _record(sys.argv[1])

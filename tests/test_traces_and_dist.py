@@ -238,6 +238,31 @@ def test_bench_two_ranks_cpu():
     assert line["config"]["global_batch"] == 8
 
 
+def test_bench_dump_outputs_repeat(tmp_path):
+    """--dump-outputs writes the last timed generation's tables and weights as
+    float64 .npy; a second run with the same arguments writes the same arrays.
+    A plain run leaves the program path and the math self-check to --full."""
+    lines = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--device", "cpu",
+                            "--steps", "3", "--warmup", "1", "--islands", "2", "--candidates", "4",
+                            "--migrate-every", "1", "--dump-outputs", str(tmp_path / d)],
+                           env=dict(os.environ, PYTHONPATH=REPO, OMP_NUM_THREADS="1"), capture_output=True, text=True,
+                           timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]))
+    assert lines[0]["steps"] == 3 and lines[0]["ms_per_step"] > 0
+    assert lines[0]["program_path"] is None and "device_math" not in lines[0]
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) == [
+        "table_r0_i0.npy", "table_r0_i1.npy", "weights_r0_i0.npy", "weights_r0_i1.npy"]
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float64 and len(a) == 4 and np.array_equal(a, b, equal_nan=True), n
+    # the champion of the run is a row of the dumped tables or of an earlier generation
+    assert max(np.load(tmp_path / "a" / n)[:, 0].max() for n in names[:2]) <= lines[0]["best_score"]
+
+
 def test_native_csv_loader_matches_python_parser():
     """C++ trace loader (csrc/cpu/trace_io.hpp) == the object-graph parser, field by field."""
     p = TraceParser()

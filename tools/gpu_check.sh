@@ -9,7 +9,7 @@
 #
 #   tests[=ARGS]        pytest -m gpu (ARGS: test files / -k expression instead of the whole suite)
 #   smoke               __graft_entry__.smoke()
-#   bench[=ARGS]        python bench.py ARGS            -> bench.json
+#   bench[=ARGS]        python bench.py --full ARGS     -> bench.json (headline and program_path)
 #   prof[=ARGS]         rocprofv3 --kernel-trace --stats of bench.py ARGS -> prof/
 #   steady=SECS[:CFG[:GENS]]  steady-state program islands for SECS seconds (CFG: configs/config3_steady.json;
 #                       GENS: generation target, so a long run keeps producing children)
@@ -47,7 +47,7 @@ for step in "$@"; do
         || die smoke "$O/smoke.txt"
       tail -1 "$O/smoke.txt" ;;
     bench)
-      timeout -k 10 600 python -u bench.py ${val//,/ } > "$O/bench.json" 2> "$O/bench.err" || die bench "$O/bench.err"
+      timeout -k 10 600 python -u bench.py --full ${val//,/ } > "$O/bench.json" 2> "$O/bench.err" || die bench "$O/bench.err"
       cut -c1-400 "$O/bench.json" ;;
     prof)
       timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$O/prof" -o run -- python3 bench.py ${val:---steps 3 --warmup 1 --programs 0 --novel 0 --novel-large 0 --evolved 0} \
