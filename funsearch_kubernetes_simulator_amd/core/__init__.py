@@ -1,7 +1,7 @@
 """L0: entity model, SoA arrays and trace I/O."""
 from .arrays import ClusterArrays, PodArrays, Workload, dense_rank
 from .model import GPU, Cluster, Node, Pod
-from .traces import TraceParser, load_default_workload, synthetic_workload
+from .traces import TraceParser, TraceSuite, load_default_workload, load_suite, synthetic_workload
 
 __all__ = ["GPU", "Node", "Cluster", "Pod", "ClusterArrays", "PodArrays", "Workload", "dense_rank",
-           "TraceParser", "load_default_workload", "synthetic_workload"]
+           "TraceParser", "TraceSuite", "load_default_workload", "load_suite", "synthetic_workload"]

@@ -185,6 +185,82 @@ def load_default_workload(traces_dir: Optional[str] = None) -> Workload:
     return TraceParser(traces_dir).load_workload()
 
 
+#: Trace-suite presets (pod-file stems after ``openb_pod_list_``), in sorted
+#: file-name order.  ``openb``: the 14 shipped traces that replay differently
+#: from one another on the 16-node cluster.
+SUITE_PRESETS: Dict[str, Tuple[str, ...]] = {
+    "openb": ("cpu037", "cpu050", "cpu072", "cpu100", "cpu200", "cpu235", "cpu250", "cpu300", "default",
+              "gpushare100", "gpushare20", "gpushare40", "gpushare60", "gpushare80"),
+}
+
+
+class TraceSuite:
+    """An ordered list of `Workload`s on one cluster, with their names."""
+
+    def __init__(self, workloads: List[Workload], names: Optional[List[str]] = None):
+        workloads = list(workloads)
+        if not workloads:
+            raise ValueError("a trace suite needs at least one workload")
+        names = list(names) if names is not None else [w.name for w in workloads]
+        if len(names) != len(workloads):
+            raise ValueError("one name per workload")
+        for w in workloads[1:]:
+            if not same_cluster(workloads[0].cluster, w.cluster):
+                raise ValueError(f"trace suite: {w.name!r} runs on another cluster than {workloads[0].name!r}")
+        self.workloads = workloads
+        self.names = names
+
+    def __len__(self) -> int:
+        return len(self.workloads)
+
+    def __iter__(self):
+        return iter(self.workloads)
+
+    def __getitem__(self, i) -> Workload:
+        return self.workloads[i]
+
+
+def same_cluster(a: ClusterArrays, b: ClusterArrays) -> bool:
+    """Same nodes, capacities, initial free resources and GPUs."""
+    if list(a.node_ids) != list(b.node_ids):
+        return False
+    return all(np.array_equal(getattr(a, f), getattr(b, f)) for f in (
+        "node_cpu_total", "node_cpu_left", "node_mem_total", "node_mem_left", "node_gpu_left", "node_ngpus",
+        "gpu_start", "gpu_milli_total", "gpu_milli_left", "gpu_mem_total", "gpu_mem_left"))
+
+
+def load_suite(names_or_preset="openb", traces_dir: Optional[str] = None,
+               node_file: str = DEFAULT_NODE_FILE) -> TraceSuite:
+    """Load several pod traces for one cluster as a `TraceSuite`.
+
+    ``names_or_preset``: a preset name (`SUITE_PRESETS`) or a list of traces,
+    each a short name (``"cpu037"``), a file stem or a file name
+    (``"openb_pod_list_cpu037.csv"``).  Every trace is paired with
+    ``node_file``; workloads on different clusters raise ``ValueError``.
+
+    The ``openb`` preset leaves out the five ``gpuspec*`` traces: ``gpu_spec``
+    is parsed and never used by the simulator, so they replay exactly like
+    ``default`` and would only weight it six times.  The four ``multigpu*``
+    files lack the time columns and raise ``KeyError`` when named, as
+    `TraceParser.parse_pods` does.
+    """
+    if isinstance(names_or_preset, str):
+        if names_or_preset not in SUITE_PRESETS:
+            raise ValueError(f"unknown suite preset {names_or_preset!r} (have {sorted(SUITE_PRESETS)})")
+        names = list(SUITE_PRESETS[names_or_preset])
+    else:
+        names = [str(n) for n in names_or_preset]
+    parser = TraceParser(traces_dir)
+    short, workloads = [], []
+    for n in names:
+        stem = Path(n).stem
+        if not stem.startswith("openb_pod_list_"):
+            stem = "openb_pod_list_" + stem
+        short.append(stem[len("openb_pod_list_"):])
+        workloads.append(parser.load_workload(node_file, stem + ".csv"))
+    return TraceSuite(workloads, short)
+
+
 def synthetic_workload(n_nodes: int = 256, n_pods: int = 65536, seed: int = 0,
                        base: Optional[Workload] = None, jitter: int = 3600) -> Workload:
     """Scaled synthetic workload (BASELINE config 5).

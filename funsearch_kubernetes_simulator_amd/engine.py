@@ -586,6 +586,136 @@ class PendingPrograms:
     deferred_idx: List[int] = field(default_factory=list)   # device rows deferred to the host (collect_partial)
 
 
+class SuiteEvaluator:
+    """Batched exact evaluator bound to a trace suite (`core.traces.load_suite`).
+
+    A host-level layer over the existing engines: it adds no device code.
+
+    ``evaluate_family`` / ``submit_family`` + ``wait`` return ``(tables, agg)``:
+    the ``[T, P, 13]`` per-trace result tables and the ``[P, 4]`` suite
+    aggregates (exact mean of the T scores, minimum, index of the first
+    minimum, traces on which the policy raised; a raising trace scores 0).
+    ``family`` is one family name or one name per policy (a mixed batch).
+    On an MI355X every trace is resident on the device with a
+    `DeviceEvaluator` of its own (``n_slots`` streams each, so T * n_slots
+    streams in all) and a batch is submitted to all of them before any is
+    waited for: one launch per trace, overlapping on the chip.  The CPU
+    backend loops the native CPU engine over the traces.  Both reduce on the
+    host with `exact_mean`.
+
+    ``evaluate_family`` is the synchronous form on slot 0: it raises while a
+    ``submit_family(0, ...)`` batch is still in flight.
+
+    ``evaluate_programs`` is CPU-only for now: one ``Evaluator(device="cpu")``
+    per trace.  The device program path for suites (one JIT module, T
+    workloads) is not built yet.
+
+    ``device``: as for `Evaluator`.
+    """
+
+    def __init__(self, suite=None, device="auto", options: Optional[dict] = None, cpu_threads: int = 0,
+                 n_slots: int = 4):
+        from .core.traces import TraceSuite, load_suite
+        if suite is None or isinstance(suite, str):
+            suite = load_suite(suite or "openb")
+        elif not isinstance(suite, TraceSuite):
+            suite = TraceSuite(list(suite))
+        self.suite = suite
+        self.names = list(suite.names)
+        self.options = dict(options or {})
+        from .ops.cpu_engine import default_threads
+        self.cpu_threads = cpu_threads or default_threads()
+        self.devices = None   # one DeviceEvaluator per trace, or None (CPU backend)
+        if device not in ("cpu", None):
+            from .ops import hip_engine
+            idx = device if isinstance(device, int) else int(os.environ.get("LOCAL_RANK", 0))
+            available = hip_engine.device_available()
+            if available and not isinstance(device, int):
+                idx %= hip_engine.native().device_count()
+            if not available and device != "auto":
+                raise RuntimeError("HIP device requested but none is visible")
+            if available:
+                built = []   # dropped as a whole if one trace does not fit the device layout
+                try:
+                    for w in suite:
+                        built.append(hip_engine.DeviceEvaluator(w, idx, self.options, n_slots))
+                    self.devices = built
+                except hip_engine.UnsupportedWorkload:
+                    del built[:]
+                    if device != "auto":
+                        raise
+        self._done: Dict[int, Tuple[np.ndarray, np.ndarray]] = {}   # CPU stand-in for in-flight slots
+        self._in_flight: set = set()   # slots holding a submitted batch
+        self._program_evaluators: Optional[List[Evaluator]] = None
+
+    def __len__(self) -> int:
+        return len(self.suite)
+
+    @property
+    def backend(self) -> str:
+        return "hip" if self.devices is not None else "cpu"
+
+    def _suite_cpu_opts(self) -> dict:
+        from .ops.cpu_engine import DEFAULT_CALL_BUDGET
+        keep = ("repush", "gpu_alloc", "snapshot_interval", "budget")
+        opts = {k: v for k, v in self.options.items() if k in keep}
+        opts.setdefault("budget", DEFAULT_CALL_BUDGET)
+        return opts
+
+    def _cpu_tables(self, family, weights) -> np.ndarray:
+        from .ops import cpu_engine
+        opts = cpu_engine.SimOptions(**self._suite_cpu_opts())
+        if isinstance(family, str):
+            return np.stack([cpu_engine.simulate_builtin_batch(w, family, weights, opts, self.cpu_threads)
+                             for w in self.suite])
+        # a mixed batch: the CPU engine takes one family per call
+        family = list(family)
+        wide = np.zeros((len(family), 16))
+        if weights is not None:
+            weights = np.asarray(weights, dtype=np.float64).reshape(len(family), -1)
+            wide[:, :weights.shape[1]] = weights
+        tables = np.zeros((len(self.suite), len(family), len(COLS)))
+        for f in sorted(set(family)):
+            idx = [i for i, g in enumerate(family) if g == f]
+            for t, w in enumerate(self.suite):
+                tables[t, idx] = cpu_engine.simulate_builtin_batch(w, f, wide[idx], opts, self.cpu_threads)
+        return tables
+
+    def evaluate_family(self, family, weights: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """(tables [T, P, 13], agg [P, 4]) for P members of a built-in family
+        (or of the families named per policy).  Synchronous, on slot 0."""
+        self.submit_family(0, family, weights)
+        return self.wait(0)
+
+    def submit_family(self, slot: int, family, weights: np.ndarray) -> None:
+        if slot in self._in_flight:
+            raise RuntimeError(f"suite slot {slot} busy: wait() for its batch first")
+        if self.devices is not None:
+            for dev in self.devices:
+                dev.submit_builtin(slot, family, weights)
+        else:
+            from .simulator.metrics import suite_aggregate
+            tables = self._cpu_tables(family, weights)
+            self._done[slot] = (tables, suite_aggregate(tables))
+        self._in_flight.add(slot)
+
+    def wait(self, slot: int) -> Tuple[np.ndarray, np.ndarray]:
+        if slot not in self._in_flight:
+            raise ValueError(f"suite slot {slot} has no batch in flight")
+        self._in_flight.discard(slot)
+        if self.devices is None:
+            return self._done.pop(slot)
+        from .simulator.metrics import suite_aggregate
+        tables = np.stack([dev.wait(slot) for dev in self.devices])
+        return tables, suite_aggregate(tables)
+
+    def evaluate_programs(self, codes: Sequence[str]) -> List[List[EvalResult]]:
+        """Per trace, the results of the program texts (CPU engines only)."""
+        if self._program_evaluators is None:
+            self._program_evaluators = [Evaluator(w, "cpu", dict(self.options), self.cpu_threads) for w in self.suite]
+        return [ev.evaluate_programs(list(codes)) for ev in self._program_evaluators]
+
+
 _default: Dict[str, Evaluator] = {}
 
 

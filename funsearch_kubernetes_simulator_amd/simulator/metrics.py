@@ -63,6 +63,26 @@ def exact_mean(values: Iterable[float]) -> float:
     return float(sum(map(Fraction, vals)) / len(vals))
 
 
+def suite_aggregate(tables) -> "np.ndarray":
+    """Suite aggregates of per-trace result tables ``[T, P, 13]`` -> ``[P, 4]``:
+    exact mean of the T scores (`exact_mean`), their minimum, the index of the
+    first minimum, and the number of traces whose replay raised (``exc != 0``).
+    A raising replay scores 0, the reference's rule for a raising policy."""
+    import numpy as np
+    from ..ops.cpu_engine import RESULT_COLUMNS
+    tables = np.asarray(tables, dtype=np.float64)
+    P = tables.shape[1]
+    raised = tables[:, :, RESULT_COLUMNS.index("exc")] != 0
+    scores = np.where(raised, 0.0, tables[:, :, RESULT_COLUMNS.index("score")])
+    agg = np.zeros((P, 4))
+    for p in range(P):
+        agg[p, 0] = exact_mean(scores[:, p].tolist())
+    agg[:, 1] = scores.min(axis=0)
+    agg[:, 2] = scores.argmin(axis=0)
+    agg[:, 3] = raised.sum(axis=0)
+    return agg
+
+
 def combine_policy_score(results: Optional[EvaluationResults], all_placed: bool) -> float:
     """The scalar fitness (`evaluator.py:101-127`)."""
     if not results:
