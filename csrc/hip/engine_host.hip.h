@@ -301,7 +301,8 @@ class DeviceEngine {
                W_.n_pods <= kRowMaxHeap && W_.tot_cpu < (int64_t(1) << 31) && W_.tot_mem < (int64_t(1) << 31) &&
                W_.tot_gcnt < (int64_t(1) << 31) && W_.tot_gmilli < (int64_t(1) << 31) &&   // int32 row totals
                max_class_pods_ < (1 << 16) &&    // 16-bit waiting-class counters
-               max_gpu_milli_ < (1 << 16);       // 16-bit GPU milli halves (NodeRegs<1, true>)
+               max_gpu_milli_ < (1 << 16) &&     // 16-bit GPU milli halves (NodeRegs<1, true>)
+               state_bounded_;                   // unsigned utilisation accumulators (RowAcc): used >= 0
     set_attrs();
   }
 
@@ -930,6 +931,19 @@ class DeviceEngine {
       if ((pw >> 16) & 0xFF) ++per_class[pw >> 24];
     }
     max_class_pods_ = *std::max_element(per_class.begin(), per_class.end());
+    {   // every free amount the cluster starts with lies in [0, its total] and no pod asks for a
+        // negative amount: used amounts then never go below 0 (the row kernels accumulate
+        // utilisation unsigned; a cluster that reports more free than total stays on the wave kernels)
+      const auto gl = i32("gpu_left"), gt = i32("gml_total"), gml = i32("gml_left");
+      bool b = ok;
+      for (int n = 0; n < nn && b; ++n) {
+        b = 0 <= cl.data()[n] && cl.data()[n] <= ct.data()[n] && 0 <= ml.data()[n] && ml.data()[n] <= mt.data()[n] &&
+            0 <= gl.data()[n] && gl.data()[n] <= ng.data()[n];
+        for (int g = 0; g < kGmax && b; ++g)
+          b = 0 <= gml.data()[(size_t)n * kGmax + g] && gml.data()[(size_t)n * kGmax + g] <= gt.data()[(size_t)n * kGmax + g];
+      }
+      state_bounded_ = b;
+    }
     {   // row kernels pack two GPUs' milli left per register (16-bit halves)
       const auto gt = i32("gml_total");
       max_gpu_milli_ = gt.size() ? *std::max_element(gt.data(), gt.data() + gt.size()) : 0;
@@ -1362,6 +1376,7 @@ class DeviceEngine {
   size_t heap_bytes_ = 0, delmap_bytes_ = 0;
   bool lds_heap_ok_ = true;
   bool rows_ok_ = false;
+  bool state_bounded_ = false;   // initial free amounts in [0, total], pod requests >= 0 (prepare_recips)
   std::string row_mode_ = "auto";
   int row_top_opt_ = -1;
   double row_share_ = 1.0;
