@@ -183,8 +183,8 @@ struct HostBuf {
 struct Slot {
   hipStream_t stream = nullptr;
   hipEvent_t done = nullptr;
-  DevBuf res, tab, fam, w, code, meta, kpay, ktag, gheap, prof, wc, queue, kc;
-  HostBuf h_in, h_tab, h_wc;
+  DevBuf res, tab, fam, w, code, meta, kpay, ktag, gheap, prof, queue, kc;
+  HostBuf h_in, h_tab;
   bool fused_table = false;   // the launch wrote h_tab itself (row kernels)
   int P = 0;
   int fam_spec = -1;    // family shared by the whole staged batch, or -1
@@ -192,10 +192,9 @@ struct Slot {
   bool busy = false;
   roctx_range_id_t range = 0;   // roctx range spanning submit -> wait (rocprofv3 --marker-trace)
   void release() {
-    for (DevBuf* b : {&res, &tab, &fam, &w, &code, &meta, &kpay, &ktag, &gheap, &prof, &wc, &queue, &kc}) b->release();
+    for (DevBuf* b : {&res, &tab, &fam, &w, &code, &meta, &kpay, &ktag, &gheap, &prof, &queue, &kc}) b->release();
     h_in.release();
     h_tab.release();
-    h_wc.release();
     if (done) (void)hipEventDestroy(done);
     if (stream) (void)hipStreamDestroy(stream);
   }
@@ -442,7 +441,7 @@ class DeviceEngine {
   py::tuple profile_native(py::array_t<uint64_t, py::array::c_style | py::array::forcecast> fn,
                            py::array_t<int64_t, py::array::c_style | py::array::forcecast> kc,
                            py::array_t<int32_t, py::array::c_style | py::array::forcecast> koff) {
-    if (!use_rows((int)fn.size())) throw std::invalid_argument("native profiling runs on the row kernel (<= 16 nodes)");
+    if (!use_rows()) throw std::invalid_argument("native profiling runs on the row kernel (<= 16 nodes)");
     submit_native_impl(0, fn, kc, koff, true);
     Slot& s = *slots_[0];
     const int waves = last_native_waves_;
@@ -482,10 +481,9 @@ class DeviceEngine {
     std::memcpy(s.h_in.as<char>() + kco, kc.data(), kb);
     std::memset(s.h_in.as<char>() + kco + kb, 0, (size_t)kKcLds * 8);
     const int64_t* kc_dev = reinterpret_cast<const int64_t*>(s.h_in.dev<char>() + kco);
-    s.h_wc.reserve(sizeof(DevWorkload));
     {
       py::gil_scoped_release rel;
-      if (use_rows(P)) {
+      if (use_rows()) {
         launch_rows_native(s, P, fb, kc_dev, profiled);
         finish(s);
         return;
@@ -496,11 +494,9 @@ class DeviceEngine {
       const size_t lds = lds_bytes(g, Wl.heap_top, kKcLds / kWave);
       if (lds > kMaxLds) throw std::invalid_argument("replay layout exceeds the 160 KiB LDS");
       uint64_t* gh = g ? gheap_for(s, P) : nullptr;
-      const fksk::NativeArgs a{Wl, upload_workload(s, Wl), s.h_in.dev<const uint64_t>(), kc_dev,
+      const fksk::NativeArgs a{Wl, nullptr, s.h_in.dev<const uint64_t>(), kc_dev,
                                reinterpret_cast<const int32_t*>(s.h_in.dev<char>() + fb), s.res.as<DevResult>(), gh};
-      if (npass_ == 1) HIP_OK(fksk::launch_native_np1(g, P, lds, s.stream, a));
-      else if (npass_ == 2) HIP_OK(fksk::launch_native_np2(g, P, lds, s.stream, a));
-      else HIP_OK(fksk::launch_native_np4(g, P, lds, s.stream, a));
+      HIP_OK(fksk::launch_native(npass_, g, P, lds, s.stream, a));
       finish(s);
     }
   }
@@ -573,8 +569,8 @@ class DeviceEngine {
     HIP_OK(hipStreamSynchronize(v.stream));
     DevWorkload Wl = W_;
     Wl.heap_top = v.T;
-    const fksk::BuiltinArgs a{Wl, nullptr, nullptr, nullptr, nullptr, v.res.as<DevResult>(), v.gheap.as<uint64_t>(),
-                              nullptr, v.tab.dev<double>()};
+    const fksk::BuiltinArgs a{Wl, nullptr, nullptr, nullptr, nullptr, v.res.as<DevResult>(), v.gheap.as<uint64_t>(), nullptr,
+                              v.tab.dev<double>()};
     const RowNativeArgs nat{v.fn.dev<const uint64_t>(), v.kc.dev<const int64_t>(), v.koff.dev<const int32_t>(),
                             v.ctl.dev<const uint32_t>() + 2, max_events_};
     // `idle_polls` polls with nothing published: the grid drains (a lost host)
@@ -815,13 +811,12 @@ class DeviceEngine {
     const DevWorkload Wl = launch_workload(g, is_vm ? nregs : 0, is_vm);
     const size_t lds = lds_bytes(g, Wl.heap_top, is_vm ? nregs : 0);
     uint64_t* gh = g ? gheap_for(s, P) : nullptr;
-    const DevWorkload* wc = upload_workload(s, Wl);
     if (is_vm) {
-      const fksk::VmArgs a{Wl, wc, table(s), s.res.as<DevResult>(), budget_, nregs, gh, s.prof.as<uint64_t>()};
+      const fksk::VmArgs a{Wl, nullptr, table(s), s.res.as<DevResult>(), budget_, nregs, gh, s.prof.as<uint64_t>()};
       HIP_OK(fksk::launch_vm_prof(g, P, lds, s.stream, a));
     } else {
       const size_t wb = (size_t)P * kWeights * 8;
-      const fksk::BuiltinArgs a{Wl, wc, reinterpret_cast<const int32_t*>(s.h_in.dev<char>() + wb),
+      const fksk::BuiltinArgs a{Wl, nullptr, reinterpret_cast<const int32_t*>(s.h_in.dev<char>() + wb),
                                 s.h_in.dev<double>(), s.w.as<double>(), s.res.as<DevResult>(), gh,
                                 s.prof.as<uint64_t>()};
       if (c5) {
@@ -896,14 +891,22 @@ class DeviceEngine {
   }
 
   bool would_use_hbm(int P) const { return use_gheap(P); }
-  bool would_use_rows(int P) const { return use_rows(P); }
+  bool would_use_rows(int) const { return use_rows(); }
   int n_slots() const { return (int)slots_.size(); }
 
  private:
   static constexpr size_t kMaxLds = 160 * 1024;
-  static constexpr int kWeightWords = kWeights;   // LDS copy of a builtin policy's weights
-  static constexpr size_t kPoliciesPerCu = 16;   // HBM-heap builtin kernels: 4 waves per SIMD
-  static constexpr size_t kVmPoliciesPerCu = 8;  // HBM-heap VM kernels: 2 waves per SIMD
+  static constexpr int kWeightWords = kWeights;   // words the kernels' LDS layout reserves in front of a policy's region
+  // Policies per CU whose LDS share an HBM-heap launch is sized for: 4 SIMDs x
+  // the waves per SIMD of the kernel instance (launch.h).  Every NPASS-1 family
+  // takes the light families' share, the heavy ones (FKS_HEAVY_WAVES) included:
+  // their heap top was measured with 16 shares per CU, and it stays that way.
+  static constexpr size_t kSimds = 4;
+  static constexpr size_t kPoliciesPerCu = kSimds * FKS_LIGHT_WAVES;
+  static constexpr size_t kNp2PoliciesPerCu = kSimds * FKS_NP2_WAVES;
+  static constexpr size_t kNp4PoliciesPerCu = kSimds * FKS_NP4_WAVES;
+  static constexpr size_t kNp4DuoPoliciesPerCu = 2 * FKS_NP4_DUO_WAVES;   // two-wave policies: 4 SIMDs x waves / 2
+  static constexpr size_t kVmPoliciesPerCu = kSimds * FKS_VM_WAVES;
 
   // Reciprocals for the row kernel's composite scorer.  A node's cpu_left
   // stays in [0, cpu_total] (likewise mem) when it starts there and no pod
@@ -1000,24 +1003,11 @@ class DeviceEngine {
     return s;
   }
 
-  void set_attrs() {
-    const int mx = (int)kMaxLds;
-    HIP_OK(fksk::set_builtin_attrs_np1(mx)); HIP_OK(fksk::set_builtin_attrs_np2(mx));
-    HIP_OK(fksk::set_builtin_attrs_np4(mx));
-    HIP_OK(fksk::set_vm_attrs_np1(mx)); HIP_OK(fksk::set_vm_attrs_np2(mx)); HIP_OK(fksk::set_vm_attrs_np4(mx));
-    HIP_OK(fksk::set_prof_attrs(mx));
-    HIP_OK(fksk::set_rows_attrs(mx));
-    HIP_OK(fksk::set_native_attrs_np1(mx)); HIP_OK(fksk::set_native_attrs_np2(mx));
-    HIP_OK(fksk::set_native_attrs_np4(mx));
-    HIP_OK(fksk::set_native_rows_attrs(mx));
-    HIP_OK(fksk::set_native_duo_attrs(mx));
-    HIP_OK(fksk::set_native_service_attrs(mx));
-  }
+  void set_attrs() { HIP_OK(fksk::set_all_attrs((int)kMaxLds)); }
 
   // 4-policies-per-wave row kernel: clusters of <= 16 nodes, exact repush
   // rule, no invariant checking (those stay on the wave kernel)
-  bool use_rows(int P) const {
-    (void)P;
+  bool use_rows() const {
     if (!rows_ok_ || row_mode_ == "off") return false;
     if (row_mode_ == "on") return true;
     return heap_mode_ != "lds" && W_.check_every == 0 && !W_.repush_earliest;
@@ -1094,13 +1084,15 @@ class DeviceEngine {
   }
 
   // HBM-heap launches keep the top 2^L - 1 heap slots in LDS, as many levels as
-  // fit a 16-policies-per-CU share of the 160 KiB (or the `heap_top` option).
+  // fit one policy's share of the 160 KiB (or the `heap_top` option).
   int heap_top_for(int nregs, bool vm, bool duo = false) const {
     const int entries = (int)(heap_bytes_ / 8);
     if (heap_top_opt_ >= 0) return std::min(heap_top_opt_, entries);
-    // (NPASS 4: FKS_NP4_WAVES waves/SIMD, or FKS_NP4_DUO_WAVES two-wave policies; NPASS 2: 3)
-    const size_t per_cu = duo ? 2 * FKS_NP4_DUO_WAVES
-                              : vm ? kVmPoliciesPerCu : (npass_ >= 4 ? 4 * FKS_NP4_WAVES : npass_ == 2 ? 12 : kPoliciesPerCu);
+    const size_t per_cu = duo            ? kNp4DuoPoliciesPerCu
+                          : vm           ? kVmPoliciesPerCu
+                          : npass_ >= 4  ? kNp4PoliciesPerCu
+                          : npass_ == 2  ? kNp2PoliciesPerCu
+                                         : kPoliciesPerCu;
     const size_t budget = kMaxLds / per_cu;
     const size_t fixed = (size_t)delmap_slots(true) / 8 + (size_t)nregs * 64 * 8 + (size_t)(W_.inv_words + kWeightWords) * 8 +
                          (duo ? fksd::wave_duo_box_bytes() : 0);
@@ -1189,7 +1181,7 @@ class DeviceEngine {
 
   void launch_builtin(Slot& s) {
     const int P = s.P;
-    if (use_rows(P)) {
+    if (use_rows()) {
       launch_rows(s, false);
       return;
     }
@@ -1202,12 +1194,10 @@ class DeviceEngine {
     if (lds > kMaxLds) throw std::invalid_argument("replay layout exceeds the 160 KiB LDS");
     uint64_t* gh = g ? gheap_for(s, P) : nullptr;
     const size_t wb = (size_t)P * kWeights * 8;
-    const fksk::BuiltinArgs a{Wl, upload_workload(s, Wl), reinterpret_cast<const int32_t*>(s.h_in.dev<char>() + wb),
+    const fksk::BuiltinArgs a{Wl, nullptr, reinterpret_cast<const int32_t*>(s.h_in.dev<char>() + wb),
                               s.h_in.dev<double>(), s.w.as<double>(), s.res.as<DevResult>(), gh, nullptr};
-    if (duo) HIP_OK(fksk::launch_builtin_duo_np4(s.fam_spec, P, lds, s.stream, a));
-    else if (npass_ == 1) HIP_OK(fksk::launch_builtin_np1(g, s.fam_spec, P, lds, s.stream, a));
-    else if (npass_ == 2) HIP_OK(fksk::launch_builtin_np2(g, s.fam_spec, P, lds, s.stream, a));
-    else HIP_OK(fksk::launch_builtin_np4(g, s.fam_spec, P, lds, s.stream, a));
+    HIP_OK(duo ? fksk::launch_builtin_wave_duo(s.fam_spec, P, lds, s.stream, a)
+               : fksk::launch_builtin(npass_, g, s.fam_spec, P, lds, s.stream, a));
   }
 
   // row kernel launch (optionally the phase-profiled build); returns the wave count
@@ -1232,7 +1222,7 @@ class DeviceEngine {
     s.gheap.reserve((size_t)row_heap_entries(W_.n_pods) * 8 * (size_t)waves * kRowsPerWave);
     if (profiled) s.prof.reserve((size_t)waves * 8 * kRowProfWords);
     const size_t wb = (size_t)P * kWeights * 8;
-    const fksk::BuiltinArgs a{Wl, upload_workload(s, Wl), reinterpret_cast<const int32_t*>(s.h_in.dev<char>() + wb),
+    const fksk::BuiltinArgs a{Wl, nullptr, reinterpret_cast<const int32_t*>(s.h_in.dev<char>() + wb),
                               s.h_in.dev<double>(), s.w.as<double>(), s.res.as<DevResult>(), s.gheap.as<uint64_t>(),
                               profiled ? s.prof.as<uint64_t>() : nullptr, s.h_tab.dev<double>()};
     s.fused_table = true;
@@ -1286,7 +1276,7 @@ class DeviceEngine {
       if (lds > kMaxLds) throw std::invalid_argument("native duo layout exceeds the 160 KiB LDS");
       s.gheap.reserve((size_t)entries * 8 * (size_t)P);
       if (profiled) s.prof.reserve((size_t)P * 128);
-      const fksk::BuiltinArgs a{Wl, upload_workload(s, Wl), nullptr, nullptr, nullptr, s.res.as<DevResult>(),
+      const fksk::BuiltinArgs a{Wl, nullptr, nullptr, nullptr, nullptr, s.res.as<DevResult>(),
                                 s.gheap.as<uint64_t>(), profiled ? s.prof.as<uint64_t>() : nullptr,
                                 s.h_tab.dev<double>()};
       s.fused_table = true;
@@ -1311,7 +1301,7 @@ class DeviceEngine {
     const int waves = std::max(1, std::min((P + ra - 1) / ra, cap));
     s.gheap.reserve((size_t)entries * 8 * (size_t)waves * kRowsPerWave);
     if (profiled) s.prof.reserve((size_t)waves * 8 * kRowProfWords);
-    const fksk::BuiltinArgs a{Wl, upload_workload(s, Wl), nullptr, nullptr, nullptr, s.res.as<DevResult>(),
+    const fksk::BuiltinArgs a{Wl, nullptr, nullptr, nullptr, nullptr, s.res.as<DevResult>(),
                               s.gheap.as<uint64_t>(), profiled ? s.prof.as<uint64_t>() : nullptr, s.h_tab.dev<double>()};
     s.fused_table = true;
     const RowNativeArgs nat{s.h_in.dev<const uint64_t>(), kc_dev,
@@ -1332,10 +1322,8 @@ class DeviceEngine {
     const size_t lds = lds_bytes(g, Wl.heap_top, nregs);
     if (lds > kMaxLds) throw std::invalid_argument("heap + VM registers exceed the 160 KiB LDS");
     uint64_t* gh = g ? gheap_for(s, P) : nullptr;
-    const fksk::VmArgs a{Wl, upload_workload(s, Wl), table(s), s.res.as<DevResult>(), budget_, nregs, gh, nullptr};
-    if (npass_ == 1) HIP_OK(fksk::launch_vm_np1(g, P, lds, s.stream, a));
-    else if (npass_ == 2) HIP_OK(fksk::launch_vm_np2(g, P, lds, s.stream, a));
-    else HIP_OK(fksk::launch_vm_np4(g, P, lds, s.stream, a));
+    const fksk::VmArgs a{Wl, nullptr, table(s), s.res.as<DevResult>(), budget_, nregs, gh, nullptr};
+    HIP_OK(fksk::launch_vm(npass_, g, P, lds, s.stream, a));
   }
 
   // the persistent-queue counter starts at zero once per slot: a copy-engine
@@ -1346,14 +1334,6 @@ class DeviceEngine {
     HIP_OK(hipMemcpyAsync(s.queue.p, zeros, 64, hipMemcpyHostToDevice, s.stream));
     HIP_OK(hipStreamSynchronize(s.stream));
   }
-
-  // The kernels read their cold workload fields from their own kernarg
-  // segment (replay_kernels.hip kernarg_workload), so a launch copies nothing
-  // to the device.  A per-slot HBM copy used to be sent with hipMemcpyAsync,
-  // which the runtime runs as a copy kernel: on a slot's first launch it had
-  // to wait for a CU slot behind the other slots' persistent replay waves
-  // (0.9-1.1 s per slot at config-5 shape, profiles/r3_config5_copy_trace.txt).
-  static const DevWorkload* upload_workload(Slot&, const DevWorkload&) { return nullptr; }
 
   // k_eval_reduce, result table -> pinned host, completion event
   void finish(Slot& s) {

@@ -7,8 +7,11 @@
 //   FKS_KIND 3 -> row kernels (4 policies per wave, <= 16 nodes; replay_rows.hip.h)
 //   FKS_KIND 4 -> native-program kernels (JIT-compiled scorers called through
 //                 function pointers; jit_abi.h) for FKS_NPASS
-// Each unit defines the matching launchers of launch.h.
+// Each unit lists its kernels in tables ({key, kernel} rows, one table per
+// group of instances) and defines the matching launchers of launch.h on them.
 #include <hip/hip_runtime.h>
+
+#include <array>
 
 #include "launch.h"
 #include "replay.hip.h"
@@ -56,7 +59,6 @@ namespace {
 //   GHEAP = true : heap in its HBM slice, LDS = bitmap | heap top (W.heap_top
 //                  slots) | vregs (16 policies/CU)
 struct Slot {
-  FKS_LDS double* w;       // builtin policy weights, copied in by the prologue
   FKS_GLOBAL uint64_t* h;
   FKS_LDS uint64_t* top;
   int T;
@@ -68,12 +70,11 @@ template <bool GHEAP>
 __device__ __forceinline__ Slot policy_slot(const DevWorkload& W, uint64_t* gheap, int p) {
   extern __shared__ uint64_t lds_raw[];
   FKS_LDS uint64_t* lds0 = lds_ptr(lds_raw);
-  // [invariant scratch | builtin weights (kWeights doubles) | policy layout]
+  // [invariant scratch | kWeights words (reserved) | policy layout]
   FKS_LDS uint64_t* lds = lds0 + W.inv_words + kWeights;
   const int N = W.n_pods;
   Slot s;
   s.inv = reinterpret_cast<FKS_LDS int32_t*>(lds0);
-  s.w = reinterpret_cast<FKS_LDS double*>(lds0 + W.inv_words);
   if (GHEAP) {
     // the deletion bitmap covers the first W.delmap_slots slots (a multiple of 64)
     const int dw = W.delmap_slots >> 5;
@@ -95,16 +96,14 @@ __device__ __forceinline__ Slot policy_slot(const DevWorkload& W, uint64_t* ghea
 // Waves per SIMD the kernel is compiled for: the LDS-heap variant is LDS-bound at
 // 2 waves/CU anyway; the HBM-heap variant trades registers for occupancy.
 #define FKS_BOUNDS(G) __launch_bounds__(64, (G) ? 4 : 1)
-// The VM keeps its hot virtual registers in VGPRs (vm_dev.hip.h): 2 waves/SIMD.
-#define FKS_VM_BOUNDS(G) __launch_bounds__(64, (G) ? 2 : 1)
+#define FKS_VM_BOUNDS(G) __launch_bounds__(64, (G) ? FKS_VM_WAVES : 1)
 
 // Prologue: the batch's family ids / weights live in pinned host memory
 // (zero-copy, no copy kernel queued behind busy CUs); each policy moves its 16
 // weights into its slot of a device buffer once, which the scorer then reads
 // through the scalar cache.
 template <int FAM>
-__device__ __forceinline__ void load_policy(BuiltinScorerDev<FAM>& sc, const Slot&, const fksk::BuiltinArgs& a,
-                                            int p) {
+__device__ __forceinline__ void load_policy(BuiltinScorerDev<FAM>& sc, const fksk::BuiltinArgs& a, int p) {
   const int lane = lane_id();
   double* wd = a.wdev + (size_t)p * kWeights;
   if (lane < kWeights) wd[lane] = a.weights[(size_t)p * kWeights + lane];
@@ -115,62 +114,74 @@ __device__ __forceinline__ void load_policy(BuiltinScorerDev<FAM>& sc, const Slo
   sc.capz = kernarg_workload()->cap_recip;
 }
 
-template <class T>
-hipError_t raise_lds(T* f, int max_lds) {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
+// ---- kernel tables ------------------------------------------------------------------------
+// A group of kernel instances is a table of rows {key, kernel}; the key is the
+// family code, the heap flag or the profiled flag.  A key the table does not
+// have takes its last row.  Every launch, LDS-limit and occupancy call of this
+// file goes through the three helpers below, so a kernel is named twice: where
+// it is defined and in its table.
+template <class... A>
+struct Row {
+  int key;
+  void (*kernel)(A...);
+};
+template <class... A, size_t N>
+auto row_kernel(const std::array<Row<A...>, N>& table, int key) {
+  for (const Row<A...>& r : table)
+    if (r.key == key) return r.kernel;
+  return table.back().kernel;
 }
+template <class Table, class... A>
+hipError_t launch_row(const Table& table, int key, dim3 grid, dim3 block, size_t lds, hipStream_t st, const A&... args) {
+  const auto kernel = row_kernel(table, key);
+  hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+  return hipGetLastError();
+}
+// the dynamic-LDS limit of every kernel of the tables, up to the first error
+template <class Table>
+hipError_t raise_lds(int max_lds, const Table& table) {
+  for (const auto& r : table) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(r.kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+template <class Table, class... More>
+hipError_t raise_lds(int max_lds, const Table& table, const More&... more) {
+  const hipError_t e = raise_lds(max_lds, table);
+  return e != hipSuccess ? e : raise_lds(max_lds, more...);
+}
+// resident workgroups of `block` threads per CU for a key's kernel at `lds` bytes (-1: error)
+template <class Table>
+int blocks_per_cu(const Table& table, int key, int block, size_t lds) {
+  int n = 0;
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, row_kernel(table, key), block, lds) == hipSuccess ? n : -1;
+}
+// the keys of a table whose rows are the instances of one kernel template
+template <int... K>
+struct Keys {};
+// the mixed-batch instance last: the row of an unknown family code
+using Families = Keys<FAM_FIRST_FIT, FAM_BEST_FIT, FAM_RANDOM_LINEAR, FAM_FEATURE_LINEAR, FAM_COMPOSITE_LINEAR, -1>;
+using Heaps = Keys<1, 0>;   // GHEAP: HBM heap, LDS heap
 
 #if FKS_KIND == 0
-// the feature families carry ~40 more live values through scoring: 3 waves/SIMD
-// without spills beats 4 with scratch traffic
-// without spills beats 4 with scratch traffic; 128 / 256 nodes (NPASS 2 / 4)
-// hold 2 / 4 node slots per lane: 3 / 2 waves per SIMD.
-#ifndef FKS_LIGHT_WAVES
-#define FKS_LIGHT_WAVES 4   // first-fit / best-fit / random_linear (build-time knob for A/B runs)
-#endif
-#ifndef FKS_HEAVY_WAVES
-#define FKS_HEAVY_WAVES 3   // feature / composite families and mixed batches
-#endif
-#define FKS_FAM_BOUNDS(G, F, NP)                                               \
-  __launch_bounds__(64, !(G) ? 1 : (NP) >= 4 ? FKS_NP4_WAVES : (NP) == 2 ? 3   \
+#define FKS_FAM_BOUNDS(G, F, NP)                                                           \
+  __launch_bounds__(64, !(G) ? 1 : (NP) >= 4 ? FKS_NP4_WAVES : (NP) == 2 ? FKS_NP2_WAVES   \
                            : (((F) == 3 || (F) == 4 || (F) < 0) ? FKS_HEAVY_WAVES : FKS_LIGHT_WAVES))
 template <int NPASS, bool GHEAP, int FAM>
 __global__ FKS_FAM_BOUNDS(GHEAP, FAM, NPASS) void k_replay_builtin(fksk::BuiltinArgs a) {
   const int p = blockIdx.x;
   const Slot s = policy_slot<GHEAP>(a.W, a.gheap, p);
   BuiltinScorerDev<FAM> sc;
-  load_policy<FAM>(sc, s, a, p);
+  load_policy<FAM>(sc, a, p);
   replay_one<NPASS, BuiltinScorerDev<FAM>, NoProf, GHEAP && FKS_WAVE_FLAT>(a.W, kernarg_workload(), sc, s.h, s.top, s.T,
                                                                            s.delmap, s.inv, a.out + p);
 }
 
-template <int NPASS, bool GHEAP>
-hipError_t launch_g(int fam, int P, size_t lds, hipStream_t st, const fksk::BuiltinArgs& a) {
-#define FKS_CASE(F) \
-  case F: hipLaunchKernelGGL((k_replay_builtin<NPASS, GHEAP, F>), dim3(P), dim3(64), lds, st, a); break;
-  switch (fam) {
-    FKS_CASE(FAM_FIRST_FIT)
-    FKS_CASE(FAM_BEST_FIT)
-    FKS_CASE(FAM_RANDOM_LINEAR)
-    FKS_CASE(FAM_FEATURE_LINEAR)
-    FKS_CASE(FAM_COMPOSITE_LINEAR)
-    default: hipLaunchKernelGGL((k_replay_builtin<NPASS, GHEAP, -1>), dim3(P), dim3(64), lds, st, a);
-  }
-#undef FKS_CASE
-  return hipGetLastError();
-}
-
-template <int NPASS, bool GHEAP>
-hipError_t attrs_g(int mx) {
-  hipError_t e = hipSuccess;
-  for (hipError_t r : {raise_lds(&k_replay_builtin<NPASS, GHEAP, -1>, mx),
-                       raise_lds(&k_replay_builtin<NPASS, GHEAP, FAM_FIRST_FIT>, mx),
-                       raise_lds(&k_replay_builtin<NPASS, GHEAP, FAM_BEST_FIT>, mx),
-                       raise_lds(&k_replay_builtin<NPASS, GHEAP, FAM_RANDOM_LINEAR>, mx),
-                       raise_lds(&k_replay_builtin<NPASS, GHEAP, FAM_FEATURE_LINEAR>, mx),
-                       raise_lds(&k_replay_builtin<NPASS, GHEAP, FAM_COMPOSITE_LINEAR>, mx)})
-    if (r != hipSuccess) e = r;
-  return e;
+template <bool GHEAP, int... F>
+constexpr std::array<Row<fksk::BuiltinArgs>, sizeof...(F)> builtin_rows(Keys<F...>) {
+  return {{{F, k_replay_builtin<FKS_NPASS, GHEAP, F>}...}};
 }
 #endif
 
@@ -183,37 +194,21 @@ __global__ __launch_bounds__(128, FKS_NP4_DUO_WAVES) void k_replay_builtin_duo(f
   const int p = blockIdx.x;
   const Slot s = policy_slot<true>(a.W, a.gheap, p);
   BuiltinScorerDev<FAM> sc;
-  if (threadIdx.x >= kWave) load_policy<FAM>(sc, s, a, p);   // the scoring wave's weights
+  if (threadIdx.x >= kWave) load_policy<FAM>(sc, a, p);   // the scoring wave's weights
   FKS_LDS DuoBox* box = reinterpret_cast<FKS_LDS DuoBox*>(lds_ptr(s.vregs));
   replay_wave_duo<4, BuiltinScorerDev<FAM>, FKS_WAVE_FLAT>(a.W, kernarg_workload(), sc, s.h, s.top, s.T, s.delmap,
                                                             box, a.out + p);
 }
 
-hipError_t launch_duo4(int fam, int P, size_t lds, hipStream_t st, const fksk::BuiltinArgs& a) {
-#define FKS_CASE(F) \
-  case F: hipLaunchKernelGGL((k_replay_builtin_duo<F>), dim3(P), dim3(128), lds, st, a); break;
-  switch (fam) {
-    FKS_CASE(FAM_FIRST_FIT)
-    FKS_CASE(FAM_BEST_FIT)
-    FKS_CASE(FAM_RANDOM_LINEAR)
-    FKS_CASE(FAM_FEATURE_LINEAR)
-    FKS_CASE(FAM_COMPOSITE_LINEAR)
-    default: hipLaunchKernelGGL((k_replay_builtin_duo<-1>), dim3(P), dim3(128), lds, st, a);
-  }
-#undef FKS_CASE
-  return hipGetLastError();
+template <int... F>
+constexpr std::array<Row<fksk::BuiltinArgs>, sizeof...(F)> builtin_duo_rows(Keys<F...>) {
+  return {{{F, k_replay_builtin_duo<F>}...}};
 }
-
-hipError_t attrs_duo4(int mx) {
-  hipError_t e = hipSuccess;
-  for (hipError_t r : {raise_lds(&k_replay_builtin_duo<-1>, mx), raise_lds(&k_replay_builtin_duo<FAM_FIRST_FIT>, mx),
-                       raise_lds(&k_replay_builtin_duo<FAM_BEST_FIT>, mx),
-                       raise_lds(&k_replay_builtin_duo<FAM_RANDOM_LINEAR>, mx),
-                       raise_lds(&k_replay_builtin_duo<FAM_FEATURE_LINEAR>, mx),
-                       raise_lds(&k_replay_builtin_duo<FAM_COMPOSITE_LINEAR>, mx)})
-    if (r != hipSuccess) e = r;
-  return e;
-}
+constexpr auto kBuiltinDuo = builtin_duo_rows(Families{});
+#endif
+#if FKS_KIND == 0
+constexpr auto kBuiltinHbm = builtin_rows<true>(Families{});
+constexpr auto kBuiltinLds = builtin_rows<false>(Families{});
 #endif
 
 #if FKS_KIND == 1
@@ -225,6 +220,11 @@ __global__ FKS_VM_BOUNDS(GHEAP) void k_replay_vm(fksk::VmArgs a) {
   sc.init(a.T, p, a.W, a.budget, s.vregs);
   replay_one<NPASS>(a.W, kernarg_workload(), sc, s.h, s.top, s.T, s.delmap, s.inv, a.out + p);
 }
+template <int... G>
+constexpr std::array<Row<fksk::VmArgs>, sizeof...(G)> vm_rows(Keys<G...>) {
+  return {{{G, k_replay_vm<FKS_NPASS, G != 0>}...}};
+}
+constexpr auto kVm = vm_rows(Heaps{});
 #endif
 
 #if FKS_KIND == 2
@@ -233,7 +233,7 @@ __global__ FKS_BOUNDS(GHEAP) void k_replay_builtin_prof(fksk::BuiltinArgs a) {
   const int p = blockIdx.x;
   const Slot s = policy_slot<GHEAP>(a.W, a.gheap, p);
   BuiltinScorerDev<-1> sc;
-  load_policy<-1>(sc, s, a, p);
+  load_policy<-1>(sc, a, p);
   replay_one<1, BuiltinScorerDev<-1>, PhaseProf>(a.W, kernarg_workload(), sc, s.h, s.top, s.T, s.delmap, s.inv, a.out + p,
                                                  a.prof + (size_t)p * 8);
 }
@@ -244,7 +244,7 @@ __global__ __launch_bounds__(64, FKS_NP4_WAVES) void k_replay_c5_prof(fksk::Buil
   const int p = blockIdx.x;
   const Slot s = policy_slot<true>(a.W, a.gheap, p);
   BuiltinScorerDev<FAM_COMPOSITE_LINEAR> sc;
-  load_policy<FAM_COMPOSITE_LINEAR>(sc, s, a, p);
+  load_policy<FAM_COMPOSITE_LINEAR>(sc, a, p);
   replay_one<4, BuiltinScorerDev<FAM_COMPOSITE_LINEAR>, PhaseProf, FKS_WAVE_FLAT>(
       a.W, kernarg_workload(), sc, s.h, s.top, s.T, s.delmap, s.inv, a.out + p, a.prof + (size_t)p * 8);
 }
@@ -257,27 +257,27 @@ __global__ FKS_VM_BOUNDS(GHEAP) void k_replay_vm_prof(fksk::VmArgs a) {
   sc.init(a.T, p, a.W, a.budget, s.vregs);
   replay_one<1, VmScorerDev, PhaseProf>(a.W, kernarg_workload(), sc, s.h, s.top, s.T, s.delmap, s.inv, a.out + p, a.prof + (size_t)p * 8);
 }
+template <int... G>
+constexpr std::array<Row<fksk::BuiltinArgs>, sizeof...(G)> builtin_prof_rows(Keys<G...>) {
+  return {{{G, k_replay_builtin_prof<G != 0>}...}};
+}
+template <int... G>
+constexpr std::array<Row<fksk::VmArgs>, sizeof...(G)> vm_prof_rows(Keys<G...>) {
+  return {{{G, k_replay_vm_prof<G != 0>}...}};
+}
+constexpr auto kBuiltinProf = builtin_prof_rows(Heaps{});
+constexpr auto kVmProf = vm_prof_rows(Heaps{});
+constexpr std::array<Row<fksk::BuiltinArgs>, 1> kC5Prof = {{{0, k_replay_c5_prof}}};
 #endif
 
 
 #if FKS_KIND == 3
-// Row kernels: the LDS share per wave (4 heap tops + bitmaps) is what bounds
-// residency; registers are capped so LDS, not VGPRs, stays the limit.
-#ifndef FKS_ROW_WAVES
-#define FKS_ROW_WAVES 5        // first-fit / best-fit / random_linear
-#endif
-#ifndef FKS_ROW_HEAVY_WAVES
-#define FKS_ROW_HEAVY_WAVES 4  // feature / composite families (composite: only loop-invariant snapshot
-                               // divisors spill, reloaded on the rare snapshot path)
-#endif
+// Row kernels (waves per SIMD: FKS_ROW_WAVES / FKS_ROW_HEAVY_WAVES, launch.h)
 template <int FAM>
 __global__ __launch_bounds__(64, FAM < 0 ? 2 : (FAM == 3 || FAM == 4) ? FKS_ROW_HEAVY_WAVES : FKS_ROW_WAVES) void k_replay_rows(fksk::BuiltinArgs a, int P, uint32_t* queue, uint32_t qbase) {
   replay_rows<FAM>(a.W, kernarg_workload(), a.fam, a.weights, a.gheap, a.out, P, queue, qbase, nullptr,
                    RowNativeArgs{nullptr, nullptr, nullptr}, kRowsPerWave, a.table);
 }
-#endif
-
-#if FKS_KIND == 3
 // The composite instance at 5 waves per SIMD (<= 96 VGPRs, a few loop-invariant
 // spills): host family code kRowCompositeW5 (`row_composite_waves` option).
 __global__ __launch_bounds__(64, 5) void k_replay_rows_c5(fksk::BuiltinArgs a, int P, uint32_t* queue, uint32_t qbase) {
@@ -296,6 +296,18 @@ void k_replay_rows_prof(fksk::BuiltinArgs a, int P, uint32_t* queue, uint32_t qb
   replay_rows<FAM, RowProf>(a.W, kernarg_workload(), a.fam, a.weights, a.gheap, a.out, P, queue, qbase, a.prof,
                             RowNativeArgs{nullptr, nullptr, nullptr}, kRowsPerWave, a.table);
 }
+using RowsRow = Row<fksk::BuiltinArgs, int, uint32_t*, uint32_t>;
+template <int... F>
+constexpr std::array<RowsRow, sizeof...(F) + 2> rows_rows(Keys<F...>) {
+  return {{{kRowCompositeW5, k_replay_rows_c5}, {kRowCompositeSplit, k_replay_rows_split}, {F, k_replay_rows<F>}...}};
+}
+template <int... F>
+constexpr std::array<RowsRow, sizeof...(F)> rows_prof_rows(Keys<F...>) {
+  return {{{F, k_replay_rows_prof<F>}...}};
+}
+constexpr auto kRows = rows_rows(Families{});
+// the profiled builds: random_linear, the one composite build, and the mixed instance for every other family
+constexpr auto kRowsProf = rows_prof_rows(Keys<FAM_RANDOM_LINEAR, FAM_COMPOSITE_LINEAR, -1>{});
 #endif
 
 
@@ -375,10 +387,8 @@ __global__ __launch_bounds__(128, 1) void k_replay_native_duo(fksk::BuiltinArgs 
 __global__ __launch_bounds__(128, 1) void k_replay_native_duo_prof(fksk::BuiltinArgs a, RowNativeArgs nat) {
   replay_duo<true>(a.W, kernarg_workload(), a.gheap, a.out, nat, a.table, a.prof);
 }
-// The resident program service (replay_duo.hip.h native_service): one workgroup
-// per resident two-wave slot, programs from the host's ring until told to stop.
 // ----------------------------------------------------------------------------
-// k_native_service: a resident pool of two-wave workgroups that replays
+// The resident program service: a resident pool of two-wave workgroups that replays
 // native programs from a ring the host keeps filling, one program after the
 // other per workgroup -- a program's replay ends, its workgroup takes the next
 // one.  A batch launch instead holds every one of its CU slots until its
@@ -400,7 +410,7 @@ __global__ __launch_bounds__(128, 1) void k_replay_native_duo_prof(fksk::Builtin
 // The replay is a call (service_replay, not inlined): inlined into the service
 // loop, values of its prologue and epilogue were hoisted out of the loop and
 // kept live across every event -- 144-156 VGPRs (6 workgroups per CU) against
-// the 128 of k_replay_native_duo.  Called, it reads every argument from the
+// the 128 of the two-wave batch kernel.  Called, it reads every argument from the
 // kernarg segment afresh and the kernel holds the two-wave kernel's 8 per CU
 // (a 224 B stack frame: the callee-saved registers, saved once per program).
 constexpr uint32_t kServiceExit = 0xFFFFFFFFu;
@@ -551,181 +561,112 @@ __global__ __launch_bounds__(64, GHEAP ? 2 : 1) void k_replay_native(fksk::Nativ
   sc.kc = kl;
   replay_one<NPASS>(a.W, kernarg_workload(), sc, s.h, s.top, s.T, s.delmap, s.inv, a.out + p);
 }
+template <int... G>
+constexpr std::array<Row<fksk::NativeArgs>, sizeof...(G)> native_rows(Keys<G...>) {
+  return {{{G, k_replay_native<FKS_NPASS, G != 0>}...}};
+}
+constexpr auto kNative = native_rows(Heaps{});
+#if FKS_NPASS == 1
+// key: the profiled flag
+constexpr std::array<Row<fksk::BuiltinArgs, RowNativeArgs, int, uint32_t*, uint32_t, int>, 2> kRowsNative = {
+    {{0, k_replay_rows_native}, {1, k_replay_rows_native_prof}}};
+constexpr std::array<Row<fksk::BuiltinArgs, RowNativeArgs>, 2> kNativeDuo = {
+    {{0, k_replay_native_duo}, {1, k_replay_native_duo_prof}}};
+constexpr std::array<Row<fksk::ServiceArgs>, 1> kService = {{{0, k_native_service}}};
+#endif
 #endif
 
 }  // namespace
 
 namespace fksk {
 
-#define FKS_CAT2(a, b) a##b
-#define FKS_CAT(a, b) FKS_CAT2(a, b)
+// Every unit defines unit_attrs for its (kind, NPASS): the LDS limit of all its
+// tables.  The wave-kernel units also define the launchers of their NPASS.
+template <int KIND, int NPASS> hipError_t unit_attrs(int max_lds);
+template <int NPASS> hipError_t unit_launch_builtin(bool gheap, int fam, int P, size_t lds, hipStream_t s, const BuiltinArgs& a);
+template <int NPASS> hipError_t unit_launch_vm(bool gheap, int P, size_t lds, hipStream_t s, const VmArgs& a);
+template <int NPASS> hipError_t unit_launch_native(bool gheap, int P, size_t lds, hipStream_t s, const NativeArgs& a);
 
 #if FKS_KIND == 0
-hipError_t FKS_CAT(launch_builtin_np, FKS_NPASS)(bool gheap, int fam, int P, size_t lds, hipStream_t s, const BuiltinArgs& a) {
-  return gheap ? launch_g<FKS_NPASS, true>(fam, P, lds, s, a) : launch_g<FKS_NPASS, false>(fam, P, lds, s, a);
-}
-hipError_t FKS_CAT(set_builtin_attrs_np, FKS_NPASS)(int mx) {
-  hipError_t e = attrs_g<FKS_NPASS, true>(mx);
-#if FKS_NPASS == 4
-  if (e == hipSuccess) e = attrs_duo4(mx);
-#endif
-  return e != hipSuccess ? e : attrs_g<FKS_NPASS, false>(mx);
+template <>
+hipError_t unit_launch_builtin<FKS_NPASS>(bool gheap, int fam, int P, size_t lds, hipStream_t s, const BuiltinArgs& a) {
+  return launch_row(gheap ? kBuiltinHbm : kBuiltinLds, fam, dim3(P), dim3(64), lds, s, a);
 }
 #if FKS_NPASS == 4
-hipError_t launch_builtin_duo_np4(int fam, int P, size_t lds, hipStream_t s, const BuiltinArgs& a) {
-  return launch_duo4(fam, P, lds, s, a);
+hipError_t launch_builtin_wave_duo(int fam, int P, size_t lds, hipStream_t s, const BuiltinArgs& a) {
+  return launch_row(kBuiltinDuo, fam, dim3(P), dim3(128), lds, s, a);
 }
 #endif
+template <>
+hipError_t unit_attrs<0, FKS_NPASS>(int mx) {
+  hipError_t e = raise_lds(mx, kBuiltinHbm, kBuiltinLds);
+#if FKS_NPASS == 4
+  if (e == hipSuccess) e = raise_lds(mx, kBuiltinDuo);
+#endif
+  return e;
+}
 #endif
 
 #if FKS_KIND == 1
-hipError_t FKS_CAT(launch_vm_np, FKS_NPASS)(bool gheap, int P, size_t lds, hipStream_t s, const VmArgs& a) {
-  if (gheap) hipLaunchKernelGGL((k_replay_vm<FKS_NPASS, true>), dim3(P), dim3(64), lds, s, a);
-  else hipLaunchKernelGGL((k_replay_vm<FKS_NPASS, false>), dim3(P), dim3(64), lds, s, a);
-  return hipGetLastError();
+template <>
+hipError_t unit_launch_vm<FKS_NPASS>(bool gheap, int P, size_t lds, hipStream_t s, const VmArgs& a) {
+  return launch_row(kVm, gheap, dim3(P), dim3(64), lds, s, a);
 }
-hipError_t FKS_CAT(set_vm_attrs_np, FKS_NPASS)(int mx) {
-  const hipError_t e = raise_lds(&k_replay_vm<FKS_NPASS, true>, mx);
-  return e != hipSuccess ? e : raise_lds(&k_replay_vm<FKS_NPASS, false>, mx);
-}
+template <>
+hipError_t unit_attrs<1, FKS_NPASS>(int mx) { return raise_lds(mx, kVm); }
 #endif
 
 #if FKS_KIND == 2
 hipError_t launch_builtin_prof(bool gheap, int P, size_t lds, hipStream_t s, const BuiltinArgs& a) {
-  if (gheap) hipLaunchKernelGGL(k_replay_builtin_prof<true>, dim3(P), dim3(64), lds, s, a);
-  else hipLaunchKernelGGL(k_replay_builtin_prof<false>, dim3(P), dim3(64), lds, s, a);
-  return hipGetLastError();
+  return launch_row(kBuiltinProf, gheap, dim3(P), dim3(64), lds, s, a);
 }
 hipError_t launch_c5_prof(int P, size_t lds, hipStream_t s, const BuiltinArgs& a) {
-  hipLaunchKernelGGL(k_replay_c5_prof, dim3(P), dim3(64), lds, s, a);
-  return hipGetLastError();
+  return launch_row(kC5Prof, 0, dim3(P), dim3(64), lds, s, a);
 }
 hipError_t launch_vm_prof(bool gheap, int P, size_t lds, hipStream_t s, const VmArgs& a) {
-  if (gheap) hipLaunchKernelGGL(k_replay_vm_prof<true>, dim3(P), dim3(64), lds, s, a);
-  else hipLaunchKernelGGL(k_replay_vm_prof<false>, dim3(P), dim3(64), lds, s, a);
-  return hipGetLastError();
+  return launch_row(kVmProf, gheap, dim3(P), dim3(64), lds, s, a);
 }
-hipError_t set_prof_attrs(int mx) {
-  hipError_t e = hipSuccess;
-  for (hipError_t r : {raise_lds(&k_replay_builtin_prof<true>, mx), raise_lds(&k_replay_builtin_prof<false>, mx),
-                       raise_lds(&k_replay_vm_prof<true>, mx), raise_lds(&k_replay_vm_prof<false>, mx),
-                       raise_lds(&k_replay_c5_prof, mx)})
-    if (r != hipSuccess) e = r;
-  return e;
-}
+template <>
+hipError_t unit_attrs<2, 1>(int mx) { return raise_lds(mx, kBuiltinProf, kVmProf, kC5Prof); }
 #endif
 
 
 #if FKS_KIND == 3
 hipError_t launch_builtin_rows(int fam, int P, int waves, uint32_t* queue, uint32_t qbase, size_t lds, hipStream_t st,
                               const BuiltinArgs& a) {
-  const dim3 grid(waves);
-#define FKS_CASE(F) \
-  case F: hipLaunchKernelGGL((k_replay_rows<F>), grid, dim3(64), lds, st, a, P, queue, qbase); break;
-  switch (fam) {
-    FKS_CASE(FAM_FIRST_FIT)
-    FKS_CASE(FAM_BEST_FIT)
-    FKS_CASE(FAM_RANDOM_LINEAR)
-    FKS_CASE(FAM_FEATURE_LINEAR)
-    FKS_CASE(FAM_COMPOSITE_LINEAR)
-    case kRowCompositeW5: hipLaunchKernelGGL(k_replay_rows_c5, grid, dim3(64), lds, st, a, P, queue, qbase); break;
-    case kRowCompositeSplit: hipLaunchKernelGGL(k_replay_rows_split, grid, dim3(64), lds, st, a, P, queue, qbase); break;
-    default: hipLaunchKernelGGL((k_replay_rows<-1>), grid, dim3(64), lds, st, a, P, queue, qbase);
-  }
-#undef FKS_CASE
-  return hipGetLastError();
+  return launch_row(kRows, fam, dim3(waves), dim3(64), lds, st, a, P, queue, qbase);
 }
-int rows_waves_per_cu(int fam, size_t lds) {
-  int n = 0;
-  hipError_t e;
-  switch (fam) {
-    case FAM_FIRST_FIT: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_replay_rows<FAM_FIRST_FIT>, 64, lds); break;
-    case FAM_BEST_FIT: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_replay_rows<FAM_BEST_FIT>, 64, lds); break;
-    case FAM_RANDOM_LINEAR:
-      e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_replay_rows<FAM_RANDOM_LINEAR>, 64, lds); break;
-    case FAM_FEATURE_LINEAR:
-      e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_replay_rows<FAM_FEATURE_LINEAR>, 64, lds); break;
-    case FAM_COMPOSITE_LINEAR:
-      e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_replay_rows<FAM_COMPOSITE_LINEAR>, 64, lds); break;
-    case kRowCompositeW5: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_replay_rows_c5, 64, lds); break;
-    case kRowCompositeSplit: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_replay_rows_split, 64, lds); break;
-    default: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_replay_rows<-1>, 64, lds);
-  }
-  return e == hipSuccess ? n : -1;
-}
+int rows_waves_per_cu(int fam, size_t lds) { return blocks_per_cu(kRows, fam, 64, lds); }
 hipError_t launch_builtin_rows_prof(int fam, int P, int waves, uint32_t* queue, uint32_t qbase, size_t lds, hipStream_t st,
                                    const BuiltinArgs& a) {
-  const dim3 grid(waves);
-  if (fam == FAM_RANDOM_LINEAR) hipLaunchKernelGGL((k_replay_rows_prof<FAM_RANDOM_LINEAR>), grid, dim3(64), lds, st, a, P, queue, qbase);
-  else if (fam == FAM_COMPOSITE_LINEAR || fam == kRowCompositeW5 || fam == kRowCompositeSplit)
-    hipLaunchKernelGGL((k_replay_rows_prof<FAM_COMPOSITE_LINEAR>), grid, dim3(64), lds, st, a, P, queue, qbase);
-  else hipLaunchKernelGGL((k_replay_rows_prof<-1>), grid, dim3(64), lds, st, a, P, queue, qbase);
-  return hipGetLastError();
+  // the three composite codes share the one profiled composite build
+  const int key = fam == kRowCompositeW5 || fam == kRowCompositeSplit ? FAM_COMPOSITE_LINEAR : fam;
+  return launch_row(kRowsProf, key, dim3(waves), dim3(64), lds, st, a, P, queue, qbase);
 }
-hipError_t set_rows_attrs(int mx) {
-  hipError_t e = hipSuccess;
-  for (hipError_t r : {raise_lds(&k_replay_rows_prof<-1>, mx), raise_lds(&k_replay_rows_prof<FAM_RANDOM_LINEAR>, mx),
-                       raise_lds(&k_replay_rows_prof<FAM_COMPOSITE_LINEAR>, mx)})
-    if (r != hipSuccess) e = r;
-  for (hipError_t r : {raise_lds(&k_replay_rows<-1>, mx), raise_lds(&k_replay_rows<FAM_FIRST_FIT>, mx),
-                       raise_lds(&k_replay_rows<FAM_BEST_FIT>, mx), raise_lds(&k_replay_rows<FAM_RANDOM_LINEAR>, mx),
-                       raise_lds(&k_replay_rows<FAM_FEATURE_LINEAR>, mx),
-                       raise_lds(&k_replay_rows<FAM_COMPOSITE_LINEAR>, mx), raise_lds(&k_replay_rows_c5, mx),
-                       raise_lds(&k_replay_rows_split, mx)})
-    if (r != hipSuccess) e = r;
-  return e;
-}
+template <>
+hipError_t unit_attrs<3, 1>(int mx) { return raise_lds(mx, kRowsProf, kRows); }
 #endif
 
 
 #if FKS_KIND == 4
-hipError_t FKS_CAT(launch_native_np, FKS_NPASS)(bool gheap, int P, size_t lds, hipStream_t s, const NativeArgs& a) {
-  if (gheap) hipLaunchKernelGGL((k_replay_native<FKS_NPASS, true>), dim3(P), dim3(64), lds, s, a);
-  else hipLaunchKernelGGL((k_replay_native<FKS_NPASS, false>), dim3(P), dim3(64), lds, s, a);
-  return hipGetLastError();
-}
-hipError_t FKS_CAT(set_native_attrs_np, FKS_NPASS)(int mx) {
-  const hipError_t e = raise_lds(&k_replay_native<FKS_NPASS, true>, mx);
-  return e != hipSuccess ? e : raise_lds(&k_replay_native<FKS_NPASS, false>, mx);
+template <>
+hipError_t unit_launch_native<FKS_NPASS>(bool gheap, int P, size_t lds, hipStream_t s, const NativeArgs& a) {
+  return launch_row(kNative, gheap, dim3(P), dim3(64), lds, s, a);
 }
 #if FKS_NPASS == 1
 hipError_t launch_native_rows(int P, int waves, int rows_active, uint32_t* queue, uint32_t qbase, size_t lds,
                               hipStream_t st, const BuiltinArgs& a, const fksd::RowNativeArgs& nat) {
-  if (a.prof) hipLaunchKernelGGL(k_replay_rows_native_prof, dim3(waves), dim3(64), lds, st, a, nat, P, queue, qbase, rows_active);
-  else hipLaunchKernelGGL(k_replay_rows_native, dim3(waves), dim3(64), lds, st, a, nat, P, queue, qbase, rows_active);
-  return hipGetLastError();
-}
-hipError_t set_native_rows_attrs(int mx) {
-  const hipError_t e = raise_lds(&k_replay_rows_native, mx);
-  return e != hipSuccess ? e : raise_lds(&k_replay_rows_native_prof, mx);
+  return launch_row(kRowsNative, a.prof != nullptr, dim3(waves), dim3(64), lds, st, a, nat, P, queue, qbase, rows_active);
 }
 hipError_t launch_native_duo(int P, size_t lds, hipStream_t st, const BuiltinArgs& a, const fksd::RowNativeArgs& nat) {
-  if (a.prof) hipLaunchKernelGGL(k_replay_native_duo_prof, dim3(P), dim3(128), lds, st, a, nat);
-  else hipLaunchKernelGGL(k_replay_native_duo, dim3(P), dim3(128), lds, st, a, nat);
-  return hipGetLastError();
-}
-hipError_t set_native_duo_attrs(int mx) {
-  const hipError_t e = raise_lds(&k_replay_native_duo, mx);
-  return e != hipSuccess ? e : raise_lds(&k_replay_native_duo_prof, mx);
+  return launch_row(kNativeDuo, a.prof != nullptr, dim3(P), dim3(128), lds, st, a, nat);
 }
 hipError_t launch_native_service(int blocks, size_t lds, hipStream_t st, const ServiceArgs& s) {
-  hipLaunchKernelGGL(k_native_service, dim3(blocks), dim3(128), lds, st, s);
-  return hipGetLastError();
+  return launch_row(kService, 0, dim3(blocks), dim3(128), lds, st, s);
 }
-// (the kernel's static LDS -- the claim word -- counts against the 160 KiB too)
-hipError_t set_native_service_attrs(int mx) { return raise_lds(&k_native_service, mx - 64); }
-int native_service_blocks_per_cu(size_t lds) {
-  int n = 0;
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_native_service, 128, lds) == hipSuccess ? n : -1;
-}
-int native_duo_blocks_per_cu(size_t lds) {
-  int n = 0;
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_replay_native_duo, 128, lds) == hipSuccess ? n : -1;
-}
-int native_rows_waves_per_cu(size_t lds) {
-  int n = 0;
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_replay_rows_native, 64, lds) == hipSuccess ? n : -1;
-}
+int native_service_blocks_per_cu(size_t lds) { return blocks_per_cu(kService, 0, 128, lds); }
+int native_duo_blocks_per_cu(size_t lds) { return blocks_per_cu(kNativeDuo, 0, 128, lds); }
+int native_rows_waves_per_cu(size_t lds) { return blocks_per_cu(kRowsNative, 0, 64, lds); }
 hipError_t native_rt_table(uint64_t* dev_out, hipStream_t s) {
   hipLaunchKernelGGL(k_native_rt_table, dim3(1), dim3(64), 0, s, dev_out);
   return hipGetLastError();
@@ -736,6 +677,50 @@ hipError_t launch_gm_batch(int fn, const double* x, const double* y, double* out
   return hipGetLastError();
 }
 #endif
+template <>
+hipError_t unit_attrs<4, FKS_NPASS>(int mx) {
+  hipError_t e = raise_lds(mx, kNative);
+#if FKS_NPASS == 1
+  if (e == hipSuccess) e = raise_lds(mx, kRowsNative, kNativeDuo);
+  // (the service kernel's static LDS -- the claim word -- counts against the 160 KiB too)
+  if (e == hipSuccess) e = raise_lds(mx - 64, kService);
+#endif
+  return e;
+}
+#endif
+
+#if FKS_KIND == 0 && FKS_NPASS == 1
+// ---- NPASS -> translation unit ------------------------------------------------------------
+// The one place that maps an NPASS value to the unit compiled for it (this
+// unit carries it for all of them), and the list of all units, which follows
+// HIP_UNITS of ops/build.py.
+template <class F>
+hipError_t for_npass(int npass, F f) {
+  switch (npass) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    default: return hipErrorInvalidValue;
+  }
+}
+hipError_t launch_builtin(int npass, bool gheap, int fam, int P, size_t lds, hipStream_t s, const BuiltinArgs& a) {
+  return for_npass(npass, [&](auto n) { return unit_launch_builtin<decltype(n)::value>(gheap, fam, P, lds, s, a); });
+}
+hipError_t launch_vm(int npass, bool gheap, int P, size_t lds, hipStream_t s, const VmArgs& a) {
+  return for_npass(npass, [&](auto n) { return unit_launch_vm<decltype(n)::value>(gheap, P, lds, s, a); });
+}
+hipError_t launch_native(int npass, bool gheap, int P, size_t lds, hipStream_t s, const NativeArgs& a) {
+  return for_npass(npass, [&](auto n) { return unit_launch_native<decltype(n)::value>(gheap, P, lds, s, a); });
+}
+hipError_t set_all_attrs(int max_lds) {
+  for (auto unit : {unit_attrs<0, 1>, unit_attrs<0, 2>, unit_attrs<0, 4>, unit_attrs<1, 1>, unit_attrs<1, 2>,
+                    unit_attrs<1, 4>, unit_attrs<2, 1>, unit_attrs<3, 1>, unit_attrs<4, 1>, unit_attrs<4, 2>,
+                    unit_attrs<4, 4>}) {
+    const hipError_t e = unit(max_lds);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
 #endif
 
 }  // namespace fksk
