@@ -258,7 +258,7 @@ using RowHeap = RowHeapT<>;
 struct RowAcc {
   uint64_t lo, hi;
   int32_t count;
-  int32_t inexact;
+  int32_t inexact;   // bit 0: lanes 0-4 the flag, lanes 5-15 the stash's; bit 1: kStashValid
   __device__ void init() { lo = hi = 0; count = 0; inexact = 0; }
   __device__ void add(int k, double v, int j) {
     const bool mine = j == k;
@@ -279,13 +279,13 @@ struct RowAcc {
       th = 0;
     }
     if (bad) {
-      if (mine) inexact = 1;
+      if (mine) inexact |= 1;
       return;
     }
     if (mine) {
       lo += tl;
       hi += th + (lo < tl);
-      if (hi >> 62) inexact = 1;   // keep LaneAcc's 2^126 headroom
+      if (hi >> 62) inexact |= 1;   // keep LaneAcc's 2^126 headroom
     }
   }
   // add() for a quotient n / d of integers 0 <= n <= d < 2^31 (utilisation
@@ -301,7 +301,41 @@ struct RowAcc {
     const uint64_t M = (bits & ((1ull << 52) - 1)) | (1ull << 52);
     const uint64_t tl = M << (s & 63), th = M >> ((64 - s) & 63);
     if (mine) {
-      if (s < 13 || s > 44) inexact = 1;
+      if (s < 13 || s > 44) inexact |= 1;
+      lo += tl;
+      hi += th + (lo < tl);
+    }
+  }
+  // The fragmentation sample of a failed placement is a function of the row's
+  // per-GPU milli left and its smallest waiting class alone, and most failures
+  // follow another failure with neither changed.  Lanes 5-15 own no
+  // accumulator, so their lo / hi / bit 0 of inexact keep what add_unit(4, v)
+  // adds for the row's last sample: the 128-bit increment and the "outside
+  // [13, 44]" flag ((0, 0, false) for +0.0).  v is row-uniform: every such
+  // lane stores the same triple.  Bit 1 of inexact, in every lane of the row,
+  // says that the stash is that of the row's present state (kStashValid).
+  static constexpr int32_t kStashValid = 2;
+  __device__ bool stash_valid() const { return (inexact & kStashValid) != 0; }
+  __device__ void stash_drop() { inexact &= ~kStashValid; }
+  __device__ void stash_unit(double v, int j) {
+    const uint64_t bits = (uint64_t)__double_as_longlong(v);
+    const int s = (int)(bits >> 52) - 979;
+    const uint64_t M = (bits & ((1ull << 52) - 1)) | (1ull << 52);
+    if (j >= 5) {
+      lo = bits == 0 ? 0ull : M << (s & 63);
+      hi = bits == 0 ? 0ull : M >> ((64 - s) & 63);
+      inexact = bits != 0 && (s < 13 || s > 44);
+    }
+    inexact |= kStashValid;
+  }
+  // add_unit(4, v) for the stashed v: lane 4 takes the triple from lane 12
+  // (a rotation by half the row, the same lane in either direction)
+  __device__ void add_stash(int j) {
+    const uint64_t tl = row_ror64<8>(lo), th = row_ror64<8>(hi);
+    const int32_t bad = (int32_t)row_ror32<8>((uint32_t)inexact) & 1;
+    if (j == 4) {
+      ++count;
+      inexact |= bad;
       lo += tl;
       hi += th + (lo < tl);
     }
@@ -571,7 +605,7 @@ __device__ void replay_rows(const DevWorkload& W, const DevWorkload* Wdev, const
     }
 #pragma unroll
     for (int k = 0; k < kRowClassSlots / 2; ++k) wcp[k] = 0u;
-    acc.init();
+    acc.init();   // (drops the fragmentation stash too: an aborted replay leaves its own behind)
     processed = 0;
     rcn[0] = 0u; rcn[1] = 0u; rcn[2] = 0u;
     const double thr = Wb->thr_after_fire;
@@ -628,6 +662,7 @@ __device__ void replay_rows(const DevWorkload& W, const DevWorkload* Wdev, const
           for (int g = 0; g < kGmax; ++g)
             if ((mask >> g) & 1) nr.g_add(0, g, pod.gmilli);
         }
+        acc.stash_drop();
         if (cold()->trace_hash) rcs[0] = mix_event(rcs[0], ((uint64_t)(uint32_t)rank << 2) | 1, (uint64_t)t);
         ecat = 1;
         prof.mark(PH_DELETE);
@@ -687,36 +722,44 @@ __device__ void replay_rows(const DevWorkload& W, const DevWorkload* Wdev, const
 
         if (best_node < 0) {
           // ---------------- failed placement
-          if (kind == kFresh && pod.ngpu > 0) {
+          const bool waits_new = kind == kFresh && pod.ngpu > 0;
+          if (waits_new) {
 #pragma unroll
             for (int sl = 0; sl < kRowClassSlots; ++sl)
               if (sl == (pod.cls >> 4) && jv == (pod.cls & 15)) wcp[sl >> 1] += 1u << (16 * (sl & 1));
           }
-          double frag = 0.0;
-          // smallest waiting class: each lane offers its lowest nonempty slot's
-          // class (sl * 16 + j), the row takes the minimum (64: none waits)
-          uint32_t nzs = 0;
+          // the sample is recomputed only when its inputs may have changed since
+          // the row's last one: a deletion or a commit in between (stash dropped
+          // there) or the histogram increment just above; a wave whose
+          // failing rows all reuse branches around the whole block
+          if (waits_new || !acc.stash_valid()) {
+            double frag = 0.0;
+            // smallest waiting class: each lane offers its lowest nonempty slot's
+            // class (sl * 16 + j), the row takes the minimum (64: none waits)
+            uint32_t nzs = 0;
 #pragma unroll
-          for (int sl = kRowClassSlots - 1; sl >= 0; --sl) nzs = wcount(sl) > 0 ? (uint32_t)sl : nzs;
-          bool any = false;
+            for (int sl = kRowClassSlots - 1; sl >= 0; --sl) nzs = wcount(sl) > 0 ? (uint32_t)sl : nzs;
+            bool any = false;
 #pragma unroll
-          for (int k = 0; k < kRowClassSlots / 2; ++k) any = any || wcp[k] != 0u;
-          const int mcls = (int)row_min_u32(any ? nzs * kRow + (uint32_t)jv : 64u);
-          if (mcls < 64) {
-            const int mv = cls_lds[mcls];
-            int32_t stranded = 0;   // the cluster's GPU milli total < 2^31 (host-checked)
+            for (int k = 0; k < kRowClassSlots / 2; ++k) any = any || wcp[k] != 0u;
+            const int mcls = (int)row_min_u32(any ? nzs * kRow + (uint32_t)jv : 64u);
+            if (mcls < 64) {
+              const int mv = cls_lds[mcls];
+              int32_t stranded = 0;   // the cluster's GPU milli total < 2^31 (host-checked)
 #pragma unroll
-            for (int g = 0; g < kGmax; ++g) {
-              const int l = nr.g(0, g);
-              if (0 < l && l < mv) stranded += l;   // GPUs past ngpus hold 0 milli (host padding)
+              for (int g = 0; g < kGmax; ++g) {
+                const int l = nr.g(0, g);
+                if (0 < l && l < mv) stranded += l;   // GPUs past ngpus hold 0 milli (host padding)
+              }
+              stranded = row_sum_i32(node_valid ? stranded : 0);
+              const int64_t tg = cold()->tot_gmilli;
+              // stranded in [0, tg]: W.z_tg is verified there
+              frag = tg <= 0 ? 0.0 : W.z_tg != 0.0 ? div_by_recip((double)stranded, W.tot_gmilli_d, W.z_tg)
+                                                   : (double)stranded / W.tot_gmilli_d;
             }
-            stranded = row_sum_i32(node_valid ? stranded : 0);
-            const int64_t tg = cold()->tot_gmilli;
-            // stranded in [0, tg]: W.z_tg is verified there
-            frag = tg <= 0 ? 0.0 : W.z_tg != 0.0 ? div_by_recip((double)stranded, W.tot_gmilli_d, W.z_tg)
-                                                 : (double)stranded / W.tot_gmilli_d;
+            acc.stash_unit(frag, jv);
           }
-          acc.add_unit(4, frag, jv);
+          acc.add_stash(jv);
           const int f = heap.first_deletion(n);
           if (f >= 0) {
             const uint64_t nt = (heap.ld(f) >> tshift) + 1;
@@ -740,6 +783,7 @@ __device__ void replay_rows(const DevWorkload& W, const DevWorkload* Wdev, const
             ok = packed >> 8;
           }
           if (!ok) { exc = EXC_ALLOC; break; }
+          acc.stash_drop();   // node state and, for a placed retry, the histogram change
           if (jv == best_node) {
             nr.cpu_left[0] -= pod.cpu;
             nr.mem_left[0] -= pod.mem;
@@ -815,7 +859,7 @@ __device__ void replay_rows(const DevWorkload& W, const DevWorkload* Wdev, const
     const int n_dropped = (int)rcn[1];
     const int64_t n_snap = row_read(acc.count, rbase, 0);
     const int64_t n_frag = row_read(acc.count, rbase, 4);
-    const int inexact = row_ballot(jv < 5 && acc.inexact != 0, rbase) != 0;
+    const int inexact = row_ballot(jv < 5 && (acc.inexact & 1) != 0, rbase) != 0;
     DevResult* o = out + p;
     if (jv < 5) {
       o->acc_lo[jv] = acc.lo;
