@@ -45,6 +45,25 @@ typedef int64_t (*ProgFn)(int32_t n_cpu_left, int32_t n_cpu_total, int32_t n_mem
                           int32_t p_cpu, int32_t p_mem, int32_t p_gpu, int64_t p_ctime, int32_t p_dur,
                           KcPtr kc);
 
+// The program call of replay_rows and of the wave kernels' NativeScorerDev
+// (replay_duo spells the same call out: its twin; the generated signature is
+// PROG_PARAMS of policy/native_codegen.py): scores node slot
+// `ps` of the calling lane's node registers for `pod`.  gmem_node: the node's
+// row of DevWorkload::gmem_total.  Returns the score (>= 0), or 0 with the
+// program's exception in `exc`.
+template <class Nodes, class Pod>
+__device__ __forceinline__ int64_t call_prog(ProgFn prog, const Nodes& nr, int ps, const Pod& pod,
+                                             const int64_t* gmem_node, KcPtr kc, int& exc) {
+  static_assert((Nodes::kPack ? 2 : 1) * Nodes::kGW == 8, "ProgFn takes the milli left / total of 8 GPUs per node");
+  const int64_t r = prog(nr.cpu_left[ps], nr.ctot(ps), nr.mem_left[ps], nr.mtot(ps),
+                         pack_gpu_ng(nr.gpu_left[ps], nr.ngp(ps)), nr.g(ps, 0), nr.g(ps, 1), nr.g(ps, 2), nr.g(ps, 3),
+                         nr.g(ps, 4), nr.g(ps, 5), nr.g(ps, 6), nr.g(ps, 7), nr.gt(ps, 0), nr.gt(ps, 1), nr.gt(ps, 2),
+                         nr.gt(ps, 3), nr.gt(ps, 4), nr.gt(ps, 5), nr.gt(ps, 6), nr.gt(ps, 7), gmem_node, pod.cpu, pod.mem,
+                         pod.gmilli | (pod.ngpu << 16), pod.ctime, pod.dur, kc);
+  if (r < 0) { exc = (int)(-r); return 0; }
+  return r;
+}
+
 // A launch's per-policy function table entry: the scorer's device address with
 // bit 0 set when the program opens with the template's feasibility prologue
 // (CompiledPolicy.feasibility_prologue): it then scores 0, with no other

@@ -292,16 +292,300 @@ __device__ bool invariants_hold(const DevWorkload& W, const Heap& heap, int n, c
 }
 
 // ----------------------------------------------------------------------------
+// The event steps of the wave kernels: replay_one runs them on the wave that
+// also owns the heap, replay_wave_duo (replay_wave_duo.hip.h) on its scoring
+// wave, with the heap on the other wave.  replay_one keeps copies of its own
+// of three of them (WaveNodes::place, fail, pick / commit).
+
+// W's copy in global memory (the kernarg segment) for the fields only
+// snapshots / failures / commits of multi-GPU pods need.  The address is made
+// opaque where it is taken (once per event), so the compiler re-loads those
+// fields (scalar-cache hits) where they are used instead of pinning ~30 SGPRs
+// for the whole loop and spilling them.
+__device__ __forceinline__ const FKS_CONST DevWorkload* cold_ptr(const DevWorkload* Wcold) {
+  const DevWorkload* g = reinterpret_cast<const DevWorkload*>(uniu64(reinterpret_cast<uint64_t>(Wcold)));
+  asm volatile("" : "+s"(g));
+  return const_ptr(g);   // scalar loads (read-only during the launch)
+}
+
+__device__ __forceinline__ int key_rank(uint64_t key, int lb, int rb) { return (int)((key >> lb) & ((1ull << rb) - 1)); }
+
+// The popped event's pod: its record (loaded by rank as soon as the key is
+// known, consumed here) and the key's time.  Wave-uniform: SGPRs.
+__device__ __forceinline__ PodView decode_pod(const DevWorkload& W, uint64_t top, int rank, const int4& precv, int tshift) {
+  PodView pod;
+  const int pw = uni(precv.w);
+  pod.cpu = uni(precv.x); pod.mem = uni(precv.y); pod.dur = uni(precv.z);
+  pod.gmilli = pw & 0xFFFF; pod.ngpu = (pw >> 16) & 0xFF; pod.cls = (pw >> 24) & 0xFF;
+  pod.ctime = (int64_t)(top >> tshift); pod.rank = rank;
+  pod.cm = W.pod_cm[rank];   // scalar load (dropped by the compiler where no scorer reads it)
+  return pod;
+}
+
+// Time of the DELETION a failed pod is re-queued one tick behind: the first
+// one in heap-array order, or (`earliest`) the earliest one; -1: none pending.
+template <class Heap>
+__device__ __forceinline__ int64_t repush_anchor(const Heap& heap, int n, bool earliest, int tshift, int lane) {
+  if (!earliest) {
+    const int f = heap.first_deletion(n);
+    return f >= 0 ? (int64_t)(uniu64(heap.ld(f)) >> tshift) : -1;
+  }
+  uint64_t mn = ~0ull;
+  for (int base = 0; base < n; base += kWave) {
+    const int i = base + lane;
+    uint64_t tv = ~0ull;
+    if (i < n) { const uint64_t k = heap.ld(i); if ((k & 3) == kDelete) tv = k >> tshift; }
+    tv = ~wave_max_u64(~tv);
+    mn = tv < mn ? tv : mn;
+  }
+  return mn == ~0ull ? -1 : (int64_t)mn;
+}
+
+// Everything of a replay but its heap, on one wave: lanes = nodes.
+// The two arrays are locals of the caller (WaveNodes<NPASS> ns{lane, nr, wcnt}),
+// as they were before the steps moved here: held as members, every NPASS 1
+// one-wave instance came out 4-9 VGPRs larger (k_replay_builtin<1, true, 0>:
+// 6 -> 5 waves per SIMD); held outside, the register counts did not move.
+constexpr int kWaitSlots = 4;   // up to 256 classes
+template <int NPASS>
+struct WaveNodes {
+  static constexpr int KP = kWaitSlots;
+  int lane;
+  NodeRegs<NPASS>& nr;
+  int32_t (&wcnt)[KP];   // waiting histogram over gpu_milli classes: class k -> lane k%64, slot k/64
+  int64_t used_cpu, used_mem, used_gcnt, used_gml;
+  LaneAcc acc;        // accumulators 0-3: utilisation snapshots, 4: fragmentation
+  int64_t processed, next_fire;
+  int ksnap, n_fire;
+  double thr;         // used once the precomputed schedule is exhausted
+  uint64_t hsh;
+  int32_t exc;
+
+  __device__ __forceinline__ void init(const DevWorkload& W) {
+    nr.cst = W.node_c4;
+#pragma unroll
+    for (int ps = 0; ps < NPASS; ++ps) {
+      const int node = ps * kWave + lane;
+      nr.cpu_left[ps] = W.cpu_left0[node];
+      nr.mem_left[ps] = W.mem_left0[node];
+      nr.gpu_left[ps] = W.gpu_left0[node];
+      if constexpr (!NodeRegs<NPASS>::kCst) {
+        nr.cpu_total[ps] = W.cpu_total[node];
+        nr.mem_total[ps] = W.mem_total[node];
+        nr.ngpus[ps] = W.ngpus[node];
+        nr.gmt1[ps] = W.gml_total[node * kGmax];
+      }
+#pragma unroll
+      for (int j = 0; j < kGmax; ++j) nr.g_init(ps, j, W.gml_left0[node * kGmax + j]);
+    }
+#pragma unroll
+    for (int k = 0; k < KP; ++k) wcnt[k] = 0;
+    used_cpu = W.used_cpu0; used_mem = W.used_mem0; used_gcnt = W.used_gcnt0; used_gml = W.used_gmilli0;
+    acc.init();
+    processed = 0;
+    ksnap = 0;
+    n_fire = W.n_fire;
+    next_fire = n_fire > 0 ? W.snap_fire[0] : INT64_MAX;
+    thr = W.thr_after_fire;
+    hsh = 0xcbf29ce484222325ull;
+    exc = EXC_NONE;
+  }
+
+  // a DELETION: the pod gives back what the key says it holds
+  __device__ __forceinline__ void remove(const DevWorkload& W, uint64_t top, const PodView& pod) {
+    const int nb = W.node_bits;
+    const int node = (int)((top >> 2) & ((1u << nb) - 1));
+    const int mask = (int)((top >> (2 + nb)) & 0xFF);
+#pragma unroll
+    for (int ps = 0; ps < NPASS; ++ps) {
+      if (ps * kWave + lane == node) {
+        nr.cpu_left[ps] += pod.cpu;
+        nr.mem_left[ps] += pod.mem;
+        nr.gpu_left[ps] += pod.ngpu;
+#pragma unroll
+        for (int j = 0; j < kGmax; ++j)
+          if ((mask >> j) & 1) nr.g_add(ps, j, pod.gmilli);
+      }
+    }
+    used_cpu -= pod.cpu; used_mem -= pod.mem; used_gcnt -= pod.ngpu;
+    used_gml -= (int64_t)pod.gmilli * __builtin_popcount(mask);
+    if (W.trace_hash) hsh = mix_event(hsh, ((uint64_t)(uint32_t)pod.rank << 2) | 1, (uint64_t)pod.ctime);
+  }
+
+  // A creation: score all nodes, argmax (first node wins ties) -> best_node,
+  // -1 when no node scores above 0 (a score of 0 never places).  false: a node
+  // raised, `exc` holds the code of the first one in node order.
+  // Each lane keeps the best of its node slots (strict >: the lowest slot
+  // wins ties) and its first exception; ONE wave max per event then finds
+  // the winning score, and the lowest node index holding it is the lowest
+  // slot whose ballot hits -- the same node as a pass-by-pass argmax, with
+  // NPASS - 1 fewer DPP reductions.
+  // (Twin: replay_one spells this step out; a change here goes there too.)
+  template <class Scorer>
+  __device__ __forceinline__ bool place(const DevWorkload& W, Scorer& scorer, const PodView& pod, int& best_node) {
+    uint64_t lbest = 0;
+    // packed per-lane state (one VGPR): bits 0-1 slot of lbest, bits 2-3
+    // slot of the first exception, bits 8+ its code (EXC_NONE = 0)
+    int lst = 0;
+#pragma unroll
+    for (int ps = 0; ps < NPASS; ++ps) {
+      const bool valid = (ps * kWave + lane) < W.n_nodes;
+      int lexc = EXC_NONE;
+      const uint64_t s = valid ? (uint64_t)scorer.template score<NPASS>(ps, nr, pod, lexc) : 0;   // >= 0
+      if (valid && lexc != EXC_NONE && (lst >> 8) == 0) lst |= (lexc << 8) | (ps << 2);
+      if (s > lbest) { lbest = s; lst = (lst & ~3) | ps; }
+    }
+    if (ballot((lst >> 8) != 0)) {
+      // the first raising node in node order (slot-major, then lane); the
+      // slots after an exception were scored too, which has no side effects
+#pragma unroll
+      for (int ps = 0; ps < NPASS; ++ps) {
+        const uint64_t b = ballot((lst >> 8) != 0 && ((lst >> 2) & 3) == ps);
+        if (b) { exc = readlane(lst >> 8, first_lane(b)); break; }
+      }
+      return false;
+    }
+    best_node = -1;
+    const uint64_t m = wave_max_u64(lbest);
+    if (m > 0) {
+#pragma unroll
+      for (int ps = NPASS - 1; ps >= 0; --ps) {
+        const uint64_t b = ballot(lbest == m && (lst & 3) == ps);
+        if (b) best_node = ps * kWave + first_lane(b);
+      }
+    }
+    return true;
+  }
+
+  // a failed placement: the pod waits (a fresh GPU pod joins the histogram);
+  // fragmentation sample = min gpu_milli over waiting GPU pods, stranded milli below it
+  // (Twin: replay_one spells this step out; a change here goes there too.)
+  __device__ __forceinline__ void fail(const FKS_CONST DevWorkload* Wc, int kind, const PodView& pod) {
+    if (kind == kFresh && pod.ngpu > 0) {
+#pragma unroll
+      for (int k = 0; k < KP; ++k)
+        if (k * kWave + lane == pod.cls) wcnt[k] += 1;
+    }
+    double frag = 0.0;
+    int mcls = -1;
+#pragma unroll
+    for (int k = 0; k < KP; ++k) {
+      const uint64_t b = ballot(wcnt[k] > 0);
+      if (mcls < 0 && b) mcls = k * kWave + first_lane(b);
+    }
+    if (mcls >= 0) {
+      const int m = const_ptr(Wc->class_value)[mcls];
+      int64_t stranded = 0;
+#pragma unroll
+      for (int ps = 0; ps < NPASS; ++ps)
+#pragma unroll
+        for (int j = 0; j < kGmax; ++j) {
+          const int l = nr.g(ps, j);
+          if (j < nr.ngp(ps) && 0 < l && l < m) stranded += l;
+        }
+      stranded = wave_sum_i64(stranded);
+      const int64_t tg = Wc->tot_gmilli;
+      frag = tg > 0 ? (double)stranded / (double)tg : 0.0;
+    }
+    acc.add(4, frag);
+  }
+
+  // the GPUs of best_node the pod takes -> gmask; false: EXC_ALLOC
+  // (Twin of pick and commit: replay_one spells both out; a change here goes there too.)
+  __device__ __forceinline__ bool pick(const FKS_CONST DevWorkload* Wc, const PodView& pod, int best_node, int& gmask) {
+    const int bp = best_node / kWave, bl = best_node % kWave;
+    gmask = 0;
+    int ok = 1;
+    if (pod.ngpu > 0) {
+      int mymask = 0, myok = 1;
+#pragma unroll
+      for (int ps = 0; ps < NPASS; ++ps)
+        if (ps == bp) mymask = pick_gpus<NPASS>(nr, ps, pod.gmilli, pod.ngpu, Wc->first_fit_alloc != 0, myok);
+      gmask = readlane(mymask, bl);
+      ok = readlane(myok, bl);
+    }
+    if (!ok) exc = EXC_ALLOC;
+    return ok;
+  }
+
+  // the placement on best_node: node registers, totals, and a placed retry leaves the histogram
+  __device__ __forceinline__ void commit(int kind, const PodView& pod, int best_node, int gmask) {
+    const int bp = best_node / kWave, bl = best_node % kWave;
+#pragma unroll
+    for (int ps = 0; ps < NPASS; ++ps) {
+      if (ps == bp && lane == bl) {
+        nr.cpu_left[ps] -= pod.cpu;
+        nr.mem_left[ps] -= pod.mem;
+        nr.gpu_left[ps] -= pod.ngpu;
+#pragma unroll
+        for (int j = 0; j < kGmax; ++j)
+          if ((gmask >> j) & 1) nr.g_add(ps, j, -pod.gmilli);
+      }
+    }
+    used_cpu += pod.cpu; used_mem += pod.mem; used_gcnt += pod.ngpu;
+    used_gml += (int64_t)pod.gmilli * __builtin_popcount(gmask);
+    if (kind == kRetry && pod.ngpu > 0) {
+#pragma unroll
+      for (int k = 0; k < KP; ++k)
+        if (k * kWave + lane == pod.cls) wcnt[k] -= 1;
+    }
+  }
+
+  // the evaluator hook after every event (snapshot schedule precomputed on the
+  // host; past it, the evaluator's own IEEE `processed / total >= threshold`)
+  __device__ __forceinline__ void snapshot(const FKS_CONST DevWorkload* Wc, int N) {
+    ++processed;
+    bool fire;
+    if (ksnap < n_fire) fire = processed >= next_fire;
+    else fire = (double)processed / (double)N >= thr;
+    if (fire) {
+      const int64_t t0 = Wc->tot_cpu, t1 = Wc->tot_mem, t2 = Wc->tot_gcnt, t3 = Wc->tot_gmilli;
+      const double r0 = t0 > 0 ? (double)used_cpu / (double)t0 : 0.0;
+      const double r1 = t1 > 0 ? (double)used_mem / (double)t1 : 0.0;
+      const double r2 = t2 > 0 ? (double)used_gcnt / (double)t2 : 0.0;
+      const double r3 = t3 > 0 ? (double)used_gml / (double)t3 : 0.0;
+      acc.add(0, r0); acc.add(1, r1); acc.add(2, r2); acc.add(3, r3);
+      if (ksnap >= n_fire) thr += Wc->snapshot_interval;
+      ++ksnap;
+      next_fire = ksnap < n_fire ? const_ptr(Wc->snap_fire)[ksnap] : INT64_MAX;
+    }
+    // (the reference's max_nodes counter feeds no metric: not tracked)
+  }
+
+  // n_repush, n_dropped: the heap owner's counters
+  __device__ __forceinline__ void write(DevResult* out, int64_t n_repush, int64_t n_dropped) {
+    const int64_t n_snap = readlane64(acc.count, 0), n_frag = readlane64(acc.count, 4);
+    const int inexact = ballot(lane < 5 && acc.inexact != 0) != 0;
+    if (lane < 5) {
+      out->acc_lo[lane] = (uint64_t)(u128)acc.sum;
+      out->acc_hi[lane] = (uint64_t)((u128)acc.sum >> 64);
+    }
+    if (lane == 0) {
+      out->n_events = processed;
+      out->n_snap = n_snap;
+      out->n_frag = n_frag;
+      out->n_unplaced = n_dropped;
+      out->n_repush = n_repush;
+      out->max_nodes = 0;
+      out->hash = hsh;
+      out->exc = exc;
+      out->inexact = inexact;
+    }
+  }
+};
+
+// ----------------------------------------------------------------------------
+// One event: pop -> decode -> delete | (place -> fail | commit) -> snapshot.
+// decode, delete, the repush time and snapshot are calls of the steps above;
+// place, fail and pick / commit are this kernel's own copies of WaveNodes'
+// (comments at each say why), held to them by the device tests alone.
 template <int NPASS, class Scorer, class Prof = NoProf, bool FLAT = false>
 __device__ void replay_one(const DevWorkload& W, const DevWorkload* Wcold, Scorer& scorer, FKS_GLOBAL uint64_t* hbuf,
                            FKS_LDS uint64_t* htop, int T, FKS_LDS uint32_t* delmap, FKS_LDS int32_t* inv,
                            DevResult* out,
                            uint64_t* prof_out = nullptr) {
   // W: the kernel-argument copy (hot fields, kept in SGPRs); Wcold: the same
-  // struct in global memory for the fields only snapshots / failures / commits
-  // of multi-GPU pods need.  Its address is made opaque once per event so the
-  // compiler re-loads those fields (scalar-cache hits) where they are used
-  // instead of pinning ~30 SGPRs for the whole loop and spilling them.
+  // struct in global memory (cold_ptr).
   // hbuf: the policy's heap array -- LDS (fast, 2 policies/CU on the 8k trace)
   // or its private slice of an HBM buffer (any trace length, 16 policies/CU);
   // slots [0, T) are held in LDS at htop instead (T >= N: all of it)
@@ -325,47 +609,17 @@ __device__ void replay_one(const DevWorkload& W, const DevWorkload* Wcold, Score
   for (int i = lane; i < (W.delmap_slots >> 5); i += kWave) heap.delmap[i] = 0u;
 
   NodeRegs<NPASS> nr;
-  nr.cst = W.node_c4;
-#pragma unroll
-  for (int ps = 0; ps < NPASS; ++ps) {
-    const int node = ps * kWave + lane;
-    nr.cpu_left[ps] = W.cpu_left0[node];
-    nr.mem_left[ps] = W.mem_left0[node];
-    nr.gpu_left[ps] = W.gpu_left0[node];
-    if constexpr (!NodeRegs<NPASS>::kCst) {
-      nr.cpu_total[ps] = W.cpu_total[node];
-      nr.mem_total[ps] = W.mem_total[node];
-      nr.ngpus[ps] = W.ngpus[node];
-      nr.gmt1[ps] = W.gml_total[node * kGmax];
-    }
-#pragma unroll
-    for (int j = 0; j < kGmax; ++j) nr.g_init(ps, j, W.gml_left0[node * kGmax + j]);
-  }
-  // waiting histogram over gpu_milli classes: class k -> lane k%64, slot k/64
-  constexpr int KP = 4;  // up to 256 classes
-  int32_t wcnt[KP];
-#pragma unroll
-  for (int k = 0; k < KP; ++k) wcnt[k] = 0;
-
-  int64_t used_cpu = W.used_cpu0, used_mem = W.used_mem0, used_gcnt = W.used_gcnt0, used_gml = W.used_gmilli0;
-  LaneAcc acc;   // accumulators 0-3: utilisation snapshots, 4: fragmentation
-  acc.init();
-  int64_t processed = 0, n_repush = 0, n_dropped = 0;
-  int ksnap = 0;
-  const int n_fire = W.n_fire;
-  int64_t next_fire = n_fire > 0 ? W.snap_fire[0] : INT64_MAX;
-  double thr = W.thr_after_fire;   // used once the precomputed schedule is exhausted
-  uint64_t hsh = 0xcbf29ce484222325ull;
-  int32_t exc = EXC_NONE;
+  int32_t wcnt[kWaitSlots];
+  WaveNodes<NPASS> ns{lane, nr, wcnt};
+  ns.init(W);
+  int64_t n_repush = 0, n_dropped = 0;
   int n = N;
   __syncthreads();
   prof.start();
 
   heap.lane = lane;
   while (n > 0) {
-    const DevWorkload* Wg = reinterpret_cast<const DevWorkload*>(uniu64(reinterpret_cast<uint64_t>(Wcold)));
-    asm volatile("" : "+s"(Wg));
-    const FKS_CONST DevWorkload* Wc = const_ptr(Wg);   // scalar loads (read-only during the launch)
+    const FKS_CONST DevWorkload* Wc = cold_ptr(Wcold);
     // Lane-derived predicates (subtree slots of the heap walk, "GPU j exists")
     // are loop-invariant; hoisted they become dozens of live 64-bit lane masks
     // in SGPRs that get spilled every event.  Opaque copies are recomputed per
@@ -386,47 +640,22 @@ __device__ void replay_one(const DevWorkload& W, const DevWorkload* Wcold, Score
     }
     // ---------------- pop (pod record load issued first, consumed after the sift)
     const uint64_t top = uniu64(heap.ld_u(0));
-    const int rank = (int)((top >> lb) & ((1ull << rb) - 1));
+    const int rank = key_rank(top, lb, rb);
     const int4 precv = load_vgpr(&W.pod[rank]);
     const uint64_t last = uniu64(heap.ld_u(n - 1));
     --n;
     if (n > 0) heap.pop_reinsert(n, last);
 
     const int kind = (int)(top & 3);
-    const int64_t t = (int64_t)(top >> tshift);
-    PodView pod;
-    const int pw = uni(precv.w);
-    pod.cpu = uni(precv.x); pod.mem = uni(precv.y); pod.dur = uni(precv.z);
-    pod.gmilli = pw & 0xFFFF; pod.ngpu = (pw >> 16) & 0xFF; pod.cls = (pw >> 24) & 0xFF;
-    pod.ctime = t; pod.rank = rank;
-    pod.cm = W.pod_cm[rank];   // scalar load (dropped by the compiler where no scorer reads it)
+    const PodView pod = decode_pod(W, top, rank, precv, tshift);
+    const int64_t t = pod.ctime;
     prof.mark(PH_POP);
 
     if (kind == kDelete) {
-      const int node = (int)((top >> 2) & ((1u << nb) - 1));
-      const int mask = (int)((top >> (2 + nb)) & 0xFF);
-#pragma unroll
-      for (int ps = 0; ps < NPASS; ++ps) {
-        if (ps * kWave + lane == node) {
-          nr.cpu_left[ps] += pod.cpu;
-          nr.mem_left[ps] += pod.mem;
-          nr.gpu_left[ps] += pod.ngpu;
-#pragma unroll
-          for (int j = 0; j < kGmax; ++j)
-            if ((mask >> j) & 1) nr.g_add(ps, j, pod.gmilli);
-        }
-      }
-      used_cpu -= pod.cpu; used_mem -= pod.mem; used_gcnt -= pod.ngpu;
-      used_gml -= (int64_t)pod.gmilli * __builtin_popcount(mask);
-      if (W.trace_hash) hsh = mix_event(hsh, ((uint64_t)(uint32_t)rank << 2) | 1, (uint64_t)t);
+      ns.remove(W, top, pod);
       prof.mark(PH_DELETE);
     } else {
-      // ---------------- creation: score all nodes, argmax (first node wins ties)
-      // Each lane keeps the best of its node slots (strict >: the lowest slot
-      // wins ties) and its first exception; ONE wave max per event then finds
-      // the winning score, and the lowest node index holding it is the lowest
-      // slot whose ballot hits -- the same node as a pass-by-pass argmax, with
-      // NPASS - 1 fewer DPP reductions.  A score of 0 never places.
+      // ---------------- creation
       if constexpr (Prof::kOn) {   // how many node slots the scorer finds feasible (diagnostics build)
         uint64_t nf = 0;
 #pragma unroll
@@ -436,6 +665,8 @@ __device__ void replay_one(const DevWorkload& W, const DevWorkload* Wcold, Score
         prof.count(7, 1);
         prof.mark(PH_POP);   // (the count's own cycles go to the pop phase)
       }
+      // score all nodes, argmax (first node wins ties): WaveNodes::place, spelled out -- through
+      // the call the mixed-family NPASS 4 instances need 128+ VGPRs and scratch
       uint64_t lbest = 0;
       // packed per-lane state (one VGPR): bits 0-1 slot of lbest, bits 2-3
       // slot of the first exception, bits 8+ its code (EXC_NONE = 0)
@@ -454,7 +685,7 @@ __device__ void replay_one(const DevWorkload& W, const DevWorkload* Wcold, Score
 #pragma unroll
         for (int ps = 0; ps < NPASS; ++ps) {
           const uint64_t b = ballot((lst >> 8) != 0 && ((lst >> 2) & 3) == ps);
-          if (b) { exc = readlane(lst >> 8, first_lane(b)); break; }
+          if (b) { ns.exc = readlane(lst >> 8, first_lane(b)); break; }
         }
         break;
       }
@@ -471,16 +702,17 @@ __device__ void replay_one(const DevWorkload& W, const DevWorkload* Wcold, Score
 
       if (best_node < 0) {
         // ---------------- failed placement
+        // WaveNodes::fail, spelled out (through the call every NPASS 4 instance needs 128+ VGPRs and scratch)
         if (kind == kFresh && pod.ngpu > 0) {
 #pragma unroll
-          for (int k = 0; k < KP; ++k)
+          for (int k = 0; k < kWaitSlots; ++k)
             if (k * kWave + lane == pod.cls) wcnt[k] += 1;
         }
         // fragmentation: min gpu_milli over waiting GPU pods, stranded milli below it
         double frag = 0.0;
         int mcls = -1;
 #pragma unroll
-        for (int k = 0; k < KP; ++k) {
+        for (int k = 0; k < kWaitSlots; ++k) {
           const uint64_t b = ballot(wcnt[k] > 0);
           if (mcls < 0 && b) mcls = k * kWave + first_lane(b);
         }
@@ -498,36 +730,22 @@ __device__ void replay_one(const DevWorkload& W, const DevWorkload* Wcold, Score
           const int64_t tg = Wc->tot_gmilli;
           frag = tg > 0 ? (double)stranded / (double)tg : 0.0;
         }
-        acc.add(4, frag);
-        // repush: first DELETION in heap-array order (or the earliest one)
-        int64_t anchor = -1;
-        if (!Wc->repush_earliest) {
-          const int f = heap.first_deletion(n);
-          if (f >= 0) anchor = (int64_t)(uniu64(heap.ld(f)) >> tshift);
-        } else {
-          uint64_t mn = ~0ull;
-          for (int base = 0; base < n; base += kWave) {
-            const int i = base + lane;
-            uint64_t tv = ~0ull;
-            if (i < n) { const uint64_t k = heap.ld(i); if ((k & 3) == kDelete) tv = k >> tshift; }
-            tv = ~wave_max_u64(~tv);
-            mn = tv < mn ? tv : mn;
-          }
-          anchor = mn == ~0ull ? -1 : (int64_t)mn;
-        }
+        ns.acc.add(4, frag);
+        const int64_t anchor = repush_anchor(heap, n, Wc->repush_earliest != 0, tshift, lane);
         if (anchor >= 0) {
           const uint64_t nt = (uint64_t)(anchor + 1);
-          if (nt > time_max) { exc = EXC_UNSUPPORTED; break; }
+          if (nt > time_max) { ns.exc = EXC_UNSUPPORTED; break; }
           heap.push(n, (nt << tshift) | ((uint64_t)rank << lb) | kRetry);
           ++n;
           ++n_repush;
         } else {
           ++n_dropped;
         }
-        if (W.trace_hash) hsh = mix_event(hsh, ((uint64_t)(uint32_t)rank << 2) | 2, (uint64_t)t);
+        if (W.trace_hash) ns.hsh = mix_event(ns.hsh, ((uint64_t)(uint32_t)rank << 2) | 2, (uint64_t)t);
         prof.mark(PH_FAIL);
       } else {
         // ---------------- commit on best_node
+        // WaveNodes::pick and commit, spelled out (through the calls the LDS-heap NPASS 4 instances lose a wave per SIMD)
         const int bp = best_node / kWave, bl = best_node % kWave;
         int gmask = 0;
         int ok = 1;
@@ -539,7 +757,7 @@ __device__ void replay_one(const DevWorkload& W, const DevWorkload* Wcold, Score
           gmask = readlane(mymask, bl);
           ok = readlane(myok, bl);
         }
-        if (!ok) { exc = EXC_ALLOC; break; }
+        if (!ok) { ns.exc = EXC_ALLOC; break; }
 #pragma unroll
         for (int ps = 0; ps < NPASS; ++ps) {
           if (ps == bp && lane == bl) {
@@ -551,66 +769,34 @@ __device__ void replay_one(const DevWorkload& W, const DevWorkload* Wcold, Score
               if ((gmask >> j) & 1) nr.g_add(ps, j, -pod.gmilli);
           }
         }
-        used_cpu += pod.cpu; used_mem += pod.mem; used_gcnt += pod.ngpu;
-        used_gml += (int64_t)pod.gmilli * __builtin_popcount(gmask);
+        ns.used_cpu += pod.cpu; ns.used_mem += pod.mem; ns.used_gcnt += pod.ngpu;
+        ns.used_gml += (int64_t)pod.gmilli * __builtin_popcount(gmask);
         if (kind == kRetry && pod.ngpu > 0) {
 #pragma unroll
-          for (int k = 0; k < KP; ++k)
+          for (int k = 0; k < kWaitSlots; ++k)
             if (k * kWave + lane == pod.cls) wcnt[k] -= 1;
         }
         const uint64_t dt = (uint64_t)(t + pod.dur);
-        if (t + pod.dur < 0 || dt > time_max) { exc = EXC_UNSUPPORTED; break; }
+        if (t + pod.dur < 0 || dt > time_max) { ns.exc = EXC_UNSUPPORTED; break; }
         heap.push(n, (dt << tshift) | ((uint64_t)rank << lb) | ((uint64_t)gmask << (2 + nb)) |
                          ((uint64_t)best_node << 2) | kDelete);
         ++n;
-        if (W.trace_hash) hsh = mix_event(hsh, ((uint64_t)(uint32_t)rank << 2), ((uint64_t)t << 8) ^ (uint64_t)best_node);
+        if (W.trace_hash) ns.hsh = mix_event(ns.hsh, ((uint64_t)(uint32_t)rank << 2), ((uint64_t)t << 8) ^ (uint64_t)best_node);
         prof.mark(PH_COMMIT);
       }
     }
 
-    // ---------------- evaluator hook (snapshot schedule precomputed on the host)
-    ++processed;
-    bool fire;
-    if (ksnap < n_fire) fire = processed >= next_fire;
-    else fire = (double)processed / (double)N >= thr;
-    if (fire) {
-      const int64_t t0 = Wc->tot_cpu, t1 = Wc->tot_mem, t2 = Wc->tot_gcnt, t3 = Wc->tot_gmilli;
-      const double r0 = t0 > 0 ? (double)used_cpu / (double)t0 : 0.0;
-      const double r1 = t1 > 0 ? (double)used_mem / (double)t1 : 0.0;
-      const double r2 = t2 > 0 ? (double)used_gcnt / (double)t2 : 0.0;
-      const double r3 = t3 > 0 ? (double)used_gml / (double)t3 : 0.0;
-      acc.add(0, r0); acc.add(1, r1); acc.add(2, r2); acc.add(3, r3);
-      if (ksnap >= n_fire) thr += Wc->snapshot_interval;
-      ++ksnap;
-      next_fire = ksnap < n_fire ? const_ptr(Wc->snap_fire)[ksnap] : INT64_MAX;
-    }
-    // (the reference's max_nodes counter feeds no metric: not tracked)
-    if (W.check_every > 0 && (processed % W.check_every == 0 || n == 0) &&
+    // ---------------- evaluator hook
+    ns.snapshot(Wc, N);
+    if (W.check_every > 0 && (ns.processed % W.check_every == 0 || n == 0) &&
         !invariants_hold<NPASS>(W, heap, n, nr, inv, lane)) {
-      exc = EXC_INVARIANT;
+      ns.exc = EXC_INVARIANT;
       break;
     }
     prof.mark(PH_EVAL);
   }
   if (prof_out) prof.flush(prof_out);
-
-  const int64_t n_snap = readlane64(acc.count, 0), n_frag = readlane64(acc.count, 4);
-  const int inexact = ballot(lane < 5 && acc.inexact != 0) != 0;
-  if (lane < 5) {
-    out->acc_lo[lane] = (uint64_t)(u128)acc.sum;
-    out->acc_hi[lane] = (uint64_t)((u128)acc.sum >> 64);
-  }
-  if (lane == 0) {
-    out->n_events = processed;
-    out->n_snap = n_snap;
-    out->n_frag = n_frag;
-    out->n_unplaced = n_dropped;
-    out->n_repush = n_repush;
-    out->max_nodes = 0;
-    out->hash = hsh;
-    out->exc = exc;
-    out->inexact = inexact;
-  }
+  ns.write(out, n_repush, n_dropped);
 }
 
 }  // namespace fksd

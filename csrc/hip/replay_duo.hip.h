@@ -66,6 +66,98 @@ __device__ __forceinline__ void duo_st(FKS_LDS uint32_t* p, uint32_t v) {
   __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
+// ---- the handshake of the two-wave kernels: called by replay_wave_duo (replay_wave_duo.hip.h), spelled out in
+// replay_duo below (its twin; the note above replay_duo says why) ----
+// `first`: this lane does the wave's stores to the box.  Every wait is a
+// bounded spin: a lost partner ends the replay with EXC_TIMEOUT, never a hang.
+
+// one lane of H, before the barrier that starts the two waves
+__device__ __forceinline__ void duo_reset(FKS_LDS DuoBox* box) {
+  box->item = 0; box->head = 0; box->tail = 0; box->rseq = 0; box->code = DUO_NONE; box->term = 0;
+  box->sabort = 0;
+  box->h_exc = EXC_NONE; box->n_repush = 0; box->n_dropped = 0;
+}
+
+// H: publish event k (a free ring slot first: S consumes in order; the
+// consumer count `tail_seen` is re-read only when the last value seen says the
+// ring may be full).  false: S gave the replay up, or the wait was lost (hexc).
+__device__ __forceinline__ bool duo_publish(FKS_LDS DuoBox* box, bool first, uint32_t k, uint32_t& tail_seen,
+                                            uint64_t key, int32_t& hexc) {
+  uint32_t spins = 0;
+  while (k - tail_seen >= (uint32_t)kDuoRing) {
+    tail_seen = duo_ld(&box->tail);
+    if (k - tail_seen < (uint32_t)kDuoRing) break;
+    if (duo_ld(&box->sabort)) return false;
+    __builtin_amdgcn_s_sleep(FKS_DUO_SLEEP);
+    if (++spins > kDuoSpinCap) { hexc = EXC_TIMEOUT; return false; }
+  }
+  if (first) box->ev[k % kDuoRing] = key;
+  if (first) duo_st(&box->head, k + 1);
+  return true;
+}
+
+// H: wait for S's answer to creation k (then in box->code / box->item).
+// false: S gave the replay up, or the wait was lost (hexc either way).
+__device__ __forceinline__ bool duo_verdict(FKS_LDS DuoBox* box, uint32_t k, int32_t& hexc) {
+  uint32_t spins = 0;
+  while (duo_ld(&box->rseq) != k + 1) {
+    if (duo_ld(&box->sabort)) { hexc = EXC_TIMEOUT; return false; }
+    __builtin_amdgcn_s_sleep(FKS_DUO_SLEEP);
+    if (++spins > kDuoSpinCap) { hexc = EXC_TIMEOUT; return false; }
+  }
+  return true;
+}
+
+// H, leaving: its exception and counters, then `term`
+__device__ __forceinline__ void duo_term(FKS_LDS DuoBox* box, int32_t hexc, int n_repush, int n_dropped) {
+  box->h_exc = hexc;
+  box->n_repush = n_repush;
+  box->n_dropped = n_dropped;
+  duo_st(&box->term, 1u);
+}
+
+// S: wait for event k.  false: H is done and published none, or the wait was lost (exc).
+__device__ __forceinline__ bool duo_next(FKS_LDS DuoBox* box, uint32_t k, int32_t& exc) {
+  uint32_t spins = 0;
+  for (;;) {
+    if (duo_ld(&box->head) > k) return true;
+    if (duo_ld(&box->term)) return duo_ld(&box->head) > k;
+    __builtin_amdgcn_s_sleep(FKS_DUO_SLEEP);
+    if (++spins > kDuoSpinCap) { exc = EXC_TIMEOUT; return false; }
+  }
+}
+// S: take event k's key (wave-uniform: SGPRs) and free its ring slot
+__device__ __forceinline__ uint64_t duo_take(FKS_LDS DuoBox* box, bool first, uint32_t k) {
+  const uint64_t top = uniu64(box->ev[k % kDuoRing]);
+  if (first) duo_st(&box->tail, k + 1);
+  return top;
+}
+
+// S: answer creation k
+__device__ __forceinline__ void duo_reply(FKS_LDS DuoBox* box, bool first, int code, uint64_t item, uint32_t k) {
+  if (first) {
+    box->item = item;
+    box->code = code;
+    duo_st(&box->rseq, k + 1);
+  }
+}
+
+// S, after its last event: H may still be pushing / scanning -- wait for it,
+// then take over its exception and counters.  true: H stopped on the last
+// event (repush time overflow) before a one-wave kernel would count it.
+__device__ __forceinline__ bool duo_join(FKS_LDS DuoBox* box, int32_t& exc, int& n_repush, int& n_dropped) {
+  uint32_t spins = 0;
+  while (!duo_ld(&box->term)) {
+    __builtin_amdgcn_s_sleep(FKS_DUO_SLEEP);
+    if (++spins > kDuoSpinCap) { exc = exc != EXC_NONE ? exc : EXC_TIMEOUT; break; }
+  }
+  const bool h_stopped = exc == EXC_NONE && box->h_exc != EXC_NONE;
+  if (h_stopped) exc = box->h_exc;
+  n_repush = box->n_repush;
+  n_dropped = box->n_dropped;
+  return h_stopped;
+}
+
 // CPython heappop's re-insertion of `last` at the root of a heap of n >= 1
 // items, walked by a whole wave: lane j < 63 is node j (BFS order) of the
 // 6-level subtree under the path end and holds that node's child pair, so a
@@ -127,6 +219,13 @@ __device__ void pop_reinsert64(const RowHeap& hp, int n, uint64_t last, int j, u
 // slot: the program's index into nat / out / table (the block index of a batch
 // launch; a ring slot under k_native_service); hslot: the HBM heap slice used
 // (per program in a batch, per resident workgroup in the service)
+// replay_duo spells out the handshake functions above, call_prog and
+// write_row_result instead of calling them: with any of them called, the
+// compiler emits other machine code for k_replay_native_duo and the service's
+// replay (the same register, scratch and LDS figures), and with all of them
+// called the service's rate was 1.5 % lower in every run
+// (profiles/r8_twin_steps_ab.txt).  As written here the two compile to the
+// machine code they had before the functions existed.
 template <bool PROF = false>
 __device__ void replay_duo(const DevWorkload& W, const DevWorkload* Wdev, uint64_t* gheap, DevResult* out,
                            RowNativeArgs nat, double* table, uint64_t* prof_out = nullptr, int slot = -1,
@@ -182,7 +281,7 @@ __device__ void replay_duo(const DevWorkload& W, const DevWorkload* Wdev, uint64
   if (wave == 0) {
     if (lane < W.n_classes) cls_lds[lane] = *global_ptr(&W.class_value[lane]);
     fill_node_tables(W, ntab, lane);
-    if (lane == 0) {
+    if (lane == 0) {   // duo_reset, spelled out (see the note above replay_duo)
       box->item = 0; box->head = 0; box->tail = 0; box->rseq = 0; box->code = DUO_NONE; box->term = 0;
       box->sabort = 0;
       box->h_exc = EXC_NONE; box->n_repush = 0; box->n_dropped = 0;
@@ -226,9 +325,9 @@ __device__ void replay_duo(const DevWorkload& W, const DevWorkload* Wdev, uint64
     int n = N, n_repush = 0, n_dropped = 0;
     int32_t hexc = EXC_NONE;
     uint32_t k = 0, tail_seen = 0;
-    // publish event k (a free ring slot first: S consumes in order; the
-    // consumer count is re-read only when the last value seen says the ring
-    // may be full)
+    // duo_publish, spelled out: event k (a free ring slot first: S consumes in
+    // order; the consumer count is re-read only when the last value seen says
+    // the ring may be full)
     auto publish = [&](uint64_t key) -> bool {
       uint32_t spins = 0;
       while (k - tail_seen >= (uint32_t)kDuoRing) {
@@ -260,7 +359,7 @@ __device__ void replay_duo(const DevWorkload& W, const DevWorkload* Wdev, uint64
       if (n > 0) pop_reinsert64(heap, n, last, lane, anc64, dir64);
       mark(2);
       if ((int)(top & 3) != kDelete) {
-        uint32_t spins = 0;
+        uint32_t spins = 0;   // duo_verdict, spelled out
         while (duo_ld(&box->rseq) != k + 1) {
           if (duo_ld(&box->sabort)) { hexc = EXC_TIMEOUT; break; }
           __builtin_amdgcn_s_sleep(FKS_DUO_SLEEP);
@@ -273,7 +372,7 @@ __device__ void replay_duo(const DevWorkload& W, const DevWorkload* Wdev, uint64
         uint64_t item = box->item;
         if (code == DUO_FAIL) {
           item = 0;
-          const int rank = (int)((top >> lb) & ((1ull << rb) - 1));
+          const int rank = key_rank(top, lb, rb);
           const int f = heap.first_deletion(n);
           if (f >= 0) {
             const uint64_t nt = (heap.ld(f) >> tshift) + 1;
@@ -303,7 +402,7 @@ __device__ void replay_duo(const DevWorkload& W, const DevWorkload* Wdev, uint64
       ++k;
     }
     flush(0);
-    if (lane == 0) {
+    if (lane == 0) {   // duo_term, spelled out
       box->h_exc = hexc;
       box->n_repush = n_repush;
       box->n_dropped = n_dropped;
@@ -380,7 +479,7 @@ __device__ void replay_duo(const DevWorkload& W, const DevWorkload* Wdev, uint64
   }
   uint64_t hsh = 0xcbf29ce484222325ull;
   int32_t exc = EXC_NONE;
-  auto reply = [&](int code, uint64_t item, uint32_t k) {
+  auto reply = [&](int code, uint64_t item, uint32_t k) {   // duo_reply, spelled out
     if (jv == 0) {
       box->item = item;
       box->code = code;
@@ -406,7 +505,7 @@ __device__ void replay_duo(const DevWorkload& W, const DevWorkload* Wdev, uint64
         break;
       }
     }
-    // next event, or the end of the replay
+    // next event, or the end of the replay (duo_next and duo_take, spelled out)
     uint32_t spins = 0;
     bool have = false;
     for (;;) {
@@ -420,7 +519,7 @@ __device__ void replay_duo(const DevWorkload& W, const DevWorkload* Wdev, uint64
     // the event and its pod are wave-uniform: SGPRs, not VGPRs across the call
     const uint64_t top = uniu64(box->ev[k % kDuoRing]);
     if (jv == 0) duo_st(&box->tail, k + 1);
-    const int rank = (int)((top >> lb) & ((1ull << rb) - 1));
+    const int rank = key_rank(top, lb, rb);
     const v4i precv = *reinterpret_cast<const FKS_GLOBAL v4i*>(global_ptr(&W.pod[rank]));
     const int kind = (int)(top & 3);
     const int64_t t = (int64_t)(top >> tshift);
@@ -455,7 +554,7 @@ __device__ void replay_duo(const DevWorkload& W, const DevWorkload* Wdev, uint64
       const NodeRegs<1> na = load_nr();   // call arguments; dead after the call
       mark(6);
       if (node_valid && (!feas_pro || feasible<1>(0, na, pod))) {
-        const NodeRegs<1>& nr = na;
+        const NodeRegs<1>& nr = na;   // call_prog (jit_abi.h), spelled out
         const int32_t* gl = nr.gw[0];   // NPASS 1: unpacked
         int32_t gt[kGmax];
 #pragma unroll
@@ -567,7 +666,7 @@ __device__ void replay_duo(const DevWorkload& W, const DevWorkload* Wdev, uint64
     ++k;
   }
   flush(1);
-  // wait for H to finish (it may still be pushing / scanning), then take its counters
+  // wait for H to finish (it may still be pushing / scanning), then take its counters (duo_join, spelled out)
   {
     uint32_t spins = 0;
     while (!duo_ld(&box->term)) {
@@ -581,7 +680,8 @@ __device__ void replay_duo(const DevWorkload& W, const DevWorkload* Wdev, uint64
   }
   const int n_repush = box->n_repush, n_dropped = box->n_dropped;
 
-  // ---------------- result (replay_rows' write-back, fused evaluator)
+  // ---------------- result: write_row_result (replay_rows.hip.h), spelled out with `!= 0` for its
+  // `& 1` (bit 1 of RowAcc::inexact, the stash flag, is never set here)
   const RowAcc acc = load_acc();
   const int64_t n_snap = row_read(acc.count, 0, 0);
   const int64_t n_frag = row_read(acc.count, 0, 4);

@@ -324,18 +324,7 @@ struct NativeScorerDev {
   __device__ int64_t score(int ps, const NodeRegs<NPASS, GP>& nr, const PodView& pod, int& exc) {
     if (feas && !feasible<NPASS, GP>(ps, nr, pod)) return 0;
     const int node = ps * kWave + lane_id();
-    int32_t gl[kGmax], gt[kGmax];
-#pragma unroll
-    for (int g = 0; g < kGmax; ++g) {
-      gl[g] = nr.g(ps, g);
-      gt[g] = nr.gt(ps, g);
-    }
-    const int64_t r = fn(nr.cpu_left[ps], nr.ctot(ps), nr.mem_left[ps], nr.mtot(ps),
-                         pack_gpu_ng(nr.gpu_left[ps], nr.ngp(ps)), gl[0], gl[1], gl[2], gl[3], gl[4], gl[5], gl[6], gl[7], gt[0], gt[1], gt[2], gt[3],
-                         gt[4], gt[5], gt[6], gt[7], gmem + (size_t)node * kGmax, pod.cpu, pod.mem,
-                         pod.gmilli | (pod.ngpu << 16), pod.ctime, pod.dur, kc);
-    if (r < 0) { exc = (int)(-r); return 0; }
-    return r;
+    return call_prog(fn, nr, ps, pod, gmem + (size_t)node * kGmax, kc, exc);
   }
 };
 

@@ -458,6 +458,69 @@ struct RowProf {
 constexpr int kRowProfBytes = 128;
 constexpr int kRowProfWords = 16;   // per wave in the host's profile buffer
 
+// The result of a row's finished (or aborted) replay (replay_duo spells the
+// same out: its twin): the DevResult and, with `table`, the evaluator fused in
+// (k_eval_reduce's arithmetic): lane k < 5 turns its own accumulator into the
+// exact mean (its count is that accumulator's), the row gathers the five
+// means, and lane c < 13 writes column c of the policy's table row.
+__device__ __forceinline__ void write_row_result(const RowAcc& acc, int jv, int rbase, int32_t processed, int32_t exc,
+                                                 int64_t n_repush, int n_dropped, uint64_t hsh, DevResult* o,
+                                                 double* table_row) {
+  const int64_t n_snap = row_read(acc.count, rbase, 0);
+  const int64_t n_frag = row_read(acc.count, rbase, 4);
+  const int inexact = row_ballot(jv < 5 && (acc.inexact & 1) != 0, rbase) != 0;   // (bit 1: the stash flag)
+  if (jv < 5) {
+    o->acc_lo[jv] = acc.lo;
+    o->acc_hi[jv] = acc.hi;
+  }
+  if (jv == 0) {
+    o->n_events = processed;
+    o->n_snap = n_snap;
+    o->n_frag = n_frag;
+    o->n_unplaced = n_dropped;
+    o->n_repush = n_repush;
+    o->max_nodes = 0;
+    o->hash = hsh;
+    o->exc = exc;
+    o->inexact = inexact;
+  }
+  if (table_row) {
+    double av = 0.0;
+    if (jv < 5 && acc.count > 0)
+      av = fixed_div_round_dev((i128)(((u128)acc.hi << 64) | acc.lo), (uint64_t)acc.count);
+    const uint64_t ab = (uint64_t)__double_as_longlong(av);
+    double avg[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+      avg[k] = __longlong_as_double((long long)(((uint64_t)(uint32_t)row_read((int)(ab >> 32), rbase, k) << 32) |
+                                                (uint32_t)row_read((int)(uint32_t)ab, rbase, k)));
+    double score = 0.0;
+    if (exc == EXC_NONE && n_snap > 0 && n_dropped == 0) {
+      const double overall = (avg[0] + avg[1] + avg[2] + avg[3]) / 4.0;
+      const double pen = avg[4] < 0.1 ? avg[4] : 0.1;
+      double sc = overall - pen;
+      sc = sc < 1.0 ? sc : 1.0;
+      score = sc > 0.0 ? sc : 0.0;
+    }
+    const bool ok = exc == EXC_NONE;   // an aborted replay reports only its exception class
+    double v = 0.0;
+    switch (jv) {
+      case 0: v = score; break;
+      case 1: case 2: case 3: case 4: case 5: v = avg[jv - 1]; break;
+      case 6: v = (double)n_snap; break;
+      case 7: v = (double)n_frag; break;
+      case 8: v = (double)processed; break;
+      case 9: v = (double)n_dropped; break;
+      case 10: v = (double)exc; break;
+      case 11: v = (double)inexact; break;
+      case 12: v = (double)(hsh >> 11); break;
+      default: break;
+    }
+    if (!ok && jv != 10) v = 0.0;
+    if (jv < 13) table_row[jv] = v;
+  }
+}
+
 // The row kernel body: a persistent work queue of policies.  Every row claims
 // policies with atomicAdd(queue, 1); a row that finishes its replay (or
 // aborts on a policy exception) writes the result and claims the next one, so
@@ -480,12 +543,7 @@ __device__ void replay_rows(const DevWorkload& W, const DevWorkload* Wdev, const
   const int ra = kNative ? rows_active : kRowsPerWave;
   // W: the kernel-argument copy, read once for the hot scalars below; every
   // other field is re-read where it is used through an opaque pointer to the
-  // HBM copy (scalar loads), so the loop carries no spilled SGPR copies of it
-  auto cold = [&]() {
-    const DevWorkload* g = reinterpret_cast<const DevWorkload*>(uniu64(reinterpret_cast<uint64_t>(Wdev)));
-    asm volatile("" : "+s"(g));
-    return const_ptr(g);
-  };
+  // HBM copy (cold_ptr(Wdev): scalar loads), so the loop carries no spilled SGPR copies of it
   extern __shared__ uint64_t lds_raw[];
   const int lane = lane_id();
   const int row = lane >> 4;
@@ -595,7 +653,7 @@ __device__ void replay_rows(const DevWorkload& W, const DevWorkload* Wdev, const
       }
     }
     for (int i = jv; i < lds_delmap_words(N); i += kRow) heap.delmap[i] = 0u;
-    const FKS_CONST DevWorkload* Wb = cold();
+    const FKS_CONST DevWorkload* Wb = cold_ptr(Wdev);
     nr.cpu_left[0] = Wb->cpu_left0[jv];
     nr.mem_left[0] = Wb->mem_left0[jv];
     nr.gpu_left[0] = Wb->gpu_left0[jv];
@@ -663,7 +721,7 @@ __device__ void replay_rows(const DevWorkload& W, const DevWorkload* Wdev, const
             if ((mask >> g) & 1) nr.g_add(0, g, pod.gmilli);
         }
         acc.stash_drop();
-        if (cold()->trace_hash) rcs[0] = mix_event(rcs[0], ((uint64_t)(uint32_t)rank << 2) | 1, (uint64_t)t);
+        if (cold_ptr(Wdev)->trace_hash) rcs[0] = mix_event(rcs[0], ((uint64_t)(uint32_t)rank << 2) | 1, (uint64_t)t);
         ecat = 1;
         prof.mark(PH_DELETE);
       } else {
@@ -680,17 +738,8 @@ __device__ void replay_rows(const DevWorkload& W, const DevWorkload* Wdev, const
         if constexpr (kNative) {
           // the program holds the template's feasibility prologue itself; one
           // that opens with it is not called for nodes feasible() rejects
-          if (node_valid && (!feas_pro || feasible<1>(0, nr, pod))) {
-            const int32_t* gl = nr.gw[0];   // NPASS 1: unpacked
-            int32_t gt[kGmax];
-#pragma unroll
-            for (int g = 0; g < kGmax; ++g) gt[g] = nr.gt(0, g);
-            s = prog(nr.cpu_left[0], nr.cpu_total[0], nr.mem_left[0], nr.mem_total[0], pack_gpu_ng(nr.gpu_left[0], nr.ngpus[0]),
-                     gl[0], gl[1], gl[2], gl[3], gl[4], gl[5], gl[6], gl[7], gt[0], gt[1], gt[2], gt[3], gt[4], gt[5],
-                     gt[6], gt[7], cold()->gmem_total + (size_t)jv * kGmax, pod.cpu, pod.mem,
-                     pod.gmilli | (pod.ngpu << 16), pod.ctime, pod.dur, kcp);
-            if (s < 0) { lexc = (int)(-s); s = 0; }
-          }
+          if (node_valid && (!feas_pro || feasible<1>(0, nr, pod)))
+            s = call_prog(prog, nr, 0, pod, cold_ptr(Wdev)->gmem_total + (size_t)jv * kGmax, kcp, lexc);
         } else if (node_valid && feasible<1>(0, nr, pod)) {
           // weights read from LDS where each term uses them (no 32-VGPR weight vector)
           const FKS_LDS double* wq = wl;
@@ -752,7 +801,7 @@ __device__ void replay_rows(const DevWorkload& W, const DevWorkload* Wdev, const
                 if (0 < l && l < mv) stranded += l;   // GPUs past ngpus hold 0 milli (host padding)
               }
               stranded = row_sum_i32(node_valid ? stranded : 0);
-              const int64_t tg = cold()->tot_gmilli;
+              const int64_t tg = cold_ptr(Wdev)->tot_gmilli;
               // stranded in [0, tg]: W.z_tg is verified there
               frag = tg <= 0 ? 0.0 : W.z_tg != 0.0 ? div_by_recip((double)stranded, W.tot_gmilli_d, W.z_tg)
                                                    : (double)stranded / W.tot_gmilli_d;
@@ -769,7 +818,7 @@ __device__ void replay_rows(const DevWorkload& W, const DevWorkload* Wdev, const
           } else {
             bump(1);
           }
-          if (cold()->trace_hash) rcs[0] = mix_event(rcs[0], ((uint64_t)(uint32_t)rank << 2) | 2, (uint64_t)t);
+          if (cold_ptr(Wdev)->trace_hash) rcs[0] = mix_event(rcs[0], ((uint64_t)(uint32_t)rank << 2) | 2, (uint64_t)t);
           ecat = 3;
           prof.mark(PH_FAIL);
         } else {
@@ -777,7 +826,7 @@ __device__ void replay_rows(const DevWorkload& W, const DevWorkload* Wdev, const
           int gmask = 0, ok = 1;
           if (pod.ngpu > 0) {
             int myok = 1;
-            const int mymask = pick_gpus<1>(nr, 0, pod.gmilli, pod.ngpu, cold()->first_fit_alloc != 0, myok);
+            const int mymask = pick_gpus<1>(nr, 0, pod.gmilli, pod.ngpu, cold_ptr(Wdev)->first_fit_alloc != 0, myok);
             const int packed = row_read(mymask | (myok << 8), rbase, best_node);
             gmask = packed & 0xFF;
             ok = packed >> 8;
@@ -801,7 +850,7 @@ __device__ void replay_rows(const DevWorkload& W, const DevWorkload* Wdev, const
           if (t + pod.dur < 0 || dt > time_max) { exc = EXC_UNSUPPORTED; break; }
           push_item = (dt << tshift) | ((uint64_t)rank << lb) | ((uint64_t)gmask << (2 + nb)) |
                       ((uint64_t)best_node << 2) | kDelete;
-          if (cold()->trace_hash)
+          if (cold_ptr(Wdev)->trace_hash)
             rcs[0] = mix_event(rcs[0], ((uint64_t)(uint32_t)rank << 2), ((uint64_t)t << 8) ^ (uint64_t)best_node);
           ecat = 2;
           prof.mark(PH_COMMIT);
@@ -817,7 +866,7 @@ __device__ void replay_rows(const DevWorkload& W, const DevWorkload* Wdev, const
       // ---------------- evaluator hook (host-precomputed snapshot schedule)
       ++processed;
       if (processed >= next_fire) {
-        const FKS_CONST DevWorkload* Ws = cold();
+        const FKS_CONST DevWorkload* Ws = cold_ptr(Wdev);
         // cluster usage = totals minus the row's sums of what is left (nodes past
         // n_nodes and GPUs past ngpus hold 0): no per-event used counters
         int32_t gl_sum = 0;
@@ -856,64 +905,8 @@ __device__ void replay_rows(const DevWorkload& W, const DevWorkload* Wdev, const
 
     if (n > 0 && exc == EXC_NONE) continue;
     // ---------------- replay done (or aborted): result, then the next policy
-    const int n_dropped = (int)rcn[1];
-    const int64_t n_snap = row_read(acc.count, rbase, 0);
-    const int64_t n_frag = row_read(acc.count, rbase, 4);
-    const int inexact = row_ballot(jv < 5 && (acc.inexact & 1) != 0, rbase) != 0;
-    DevResult* o = out + p;
-    if (jv < 5) {
-      o->acc_lo[jv] = acc.lo;
-      o->acc_hi[jv] = acc.hi;
-    }
-    if (jv == 0) {
-      o->n_events = processed;
-      o->n_snap = n_snap;
-      o->n_frag = n_frag;
-      o->n_unplaced = n_dropped;
-      o->n_repush = (int64_t)rcn[0];
-      o->max_nodes = 0;
-      o->hash = rcs[0];
-      o->exc = exc;
-      o->inexact = inexact;
-    }
-    if (table) {
-      // the evaluator (k_eval_reduce's arithmetic, fused): lane k < 5 turns its
-      // own accumulator into the exact mean (its count is that accumulator's),
-      // the row gathers the five means, and lane c < 13 writes column c
-      double av = 0.0;
-      if (jv < 5 && acc.count > 0)
-        av = fixed_div_round_dev((i128)(((u128)acc.hi << 64) | acc.lo), (uint64_t)acc.count);
-      const uint64_t ab = (uint64_t)__double_as_longlong(av);
-      double avg[5];
-#pragma unroll
-      for (int k = 0; k < 5; ++k)
-        avg[k] = __longlong_as_double((long long)(((uint64_t)(uint32_t)row_read((int)(ab >> 32), rbase, k) << 32) |
-                                                  (uint32_t)row_read((int)(uint32_t)ab, rbase, k)));
-      double score = 0.0;
-      if (exc == EXC_NONE && n_snap > 0 && n_dropped == 0) {
-        const double overall = (avg[0] + avg[1] + avg[2] + avg[3]) / 4.0;
-        const double pen = avg[4] < 0.1 ? avg[4] : 0.1;
-        double sc = overall - pen;
-        sc = sc < 1.0 ? sc : 1.0;
-        score = sc > 0.0 ? sc : 0.0;
-      }
-      const bool ok = exc == EXC_NONE;   // an aborted replay reports only its exception class
-      double v = 0.0;
-      switch (jv) {
-        case 0: v = score; break;
-        case 1: case 2: case 3: case 4: case 5: v = avg[jv - 1]; break;
-        case 6: v = (double)n_snap; break;
-        case 7: v = (double)n_frag; break;
-        case 8: v = (double)processed; break;
-        case 9: v = (double)n_dropped; break;
-        case 10: v = (double)exc; break;
-        case 11: v = (double)inexact; break;
-        case 12: v = (double)(rcs[0] >> 11); break;
-        default: break;
-      }
-      if (!ok && jv != 10) v = 0.0;
-      if (jv < 13) table[(size_t)p * 13 + jv] = v;
-    }
+    write_row_result(acc, jv, rbase, processed, exc, (int64_t)rcn[0], (int)rcn[1], rcs[0], out + p,
+                     table ? table + (size_t)p * 13 : nullptr);
     p = claim();
     have = p < P;
     if (have) begin();

@@ -49,7 +49,8 @@ import numpy as np
 from .bytecode import NO_REG, TAG_FLOAT, Op, unpack_code
 from .compiler import CompiledPolicy
 
-#: parameter list shared by every generated program (keep in sync with jit_abi.h ProgFn)
+#: parameter list shared by every generated program (keep in sync with jit_abi.h: the ProgFn type and
+#: call_prog, which passes these arguments; replay_duo.hip.h spells the same call out once more)
 #: (31 argument dwords: v0-v30 -- v31 carries the work-item ids, so a 32nd
 #: dword would travel through the stack, i.e. a scratch store + load per call;
 #: the node's free-GPU count and GPU count share one dword)

@@ -293,12 +293,29 @@ def expected_info(name: str) -> dict:
     return out
 
 
+#: families with an "aborts_<family>" batch (`abort_rows` of the family's first candidate)
+ABORT_FAMILIES = ("random_linear", "feature_linear")
+ABORT_BATCHES = tuple(f"aborts_{f}" for f in ABORT_FAMILIES)
+
+
+def abort_rows(row: np.ndarray) -> np.ndarray:
+    """Five rows: `row`, `row` with w[0] = inf, with w[0] = nan, `row` scaled
+    by 1e290 and by 1e306 -- a clean replay beside three exception classes."""
+    out = np.tile(np.asarray(row, dtype=np.float64), (5, 1))
+    out[1, 0], out[2, 0] = np.inf, np.nan
+    out[3] *= 1e290
+    with np.errstate(over="ignore"):   # weights above 1e2 become inf
+        out[4] *= 1e306
+    return out
+
+
 @functools.lru_cache(maxsize=None)
 def candidates():
     """The builtin batches every shape is scored on: name -> (family or list
     of families, weights [P, 16] or None).  The first `N_CANDIDATES` rows of a
     weighted family are its candidates; the composite batch adds an all-zero
-    row and a -0.0 row; no batch size is a multiple of 4."""
+    row and a -0.0 row; the "aborts" batches hold rows that raise; no batch
+    size is a multiple of 4."""
     rng = np.random.default_rng(2024)
     out = {"first_fit": ("first_fit", np.zeros((3, 16))), "best_fit": ("best_fit", np.zeros((3, 16)))}
     for f in FAMILIES:
@@ -314,6 +331,10 @@ def candidates():
         if f in FAMILIES:
             W[i] = out[f][1][i]
     out["mixed"] = (names, W)
+    # rows that raise: the sampled candidates never do, so these alone reach the
+    # kernels' first-exception selection and the two-wave kernels' abort replies
+    for f in ABORT_FAMILIES:
+        out[f"aborts_{f}"] = (f, abort_rows(out[f][1][0]))
     assert all(len(w) % 4 for _, w in out.values())
     for _, w in out.values():
         w.setflags(write=False)

@@ -106,6 +106,19 @@ def test_candidates_are_told_apart_and_placements_fail(name):
         assert 2 * distinct >= ds.N_CANDIDATES and 4 * frag >= ds.N_CANDIDATES, (family, distinct, frag)
 
 
+@pytest.mark.parametrize("name", ("sweep129", "sweep255"))
+def test_abort_batches_raise_three_exception_classes(name):
+    """The "aborts" batches on the shapes the two-wave builtin kernel takes: the
+    sampled row replays clean and scores, the other four raise, in at least
+    three exception classes."""
+    for batch in ds.ABORT_BATCHES:
+        family, weights = ds.candidates()[batch]
+        tab = ce.simulate_builtin_batch(ds.shape(name), family, weights)
+        assert tab[0, 10] == 0 and tab[0, 0] > 0, (batch, tab[0].tolist())
+        assert tab[1:, 10].all() and len(set(tab[1:, 10].tolist())) >= 3, (batch, tab[:, 10].tolist())
+        assert not tab[1:, 0].any(), batch
+
+
 @pytest.mark.parametrize("n", (13, 70))
 def test_zero_request_pods_matter(n):
     a, b = ds.zero_requests(n), ds.zero_requests(n, with_zero_pods=False)

@@ -18,7 +18,7 @@ from funsearch_kubernetes_simulator_amd.simulator.metrics import suite_aggregate
 
 pytestmark = pytest.mark.gpu
 
-BATCHES = ("first_fit", "best_fit") + ds.FAMILIES + ("mixed",)
+BATCHES = ("first_fit", "best_fit") + ds.FAMILIES + ("mixed",) + ds.ABORT_BATCHES
 #: one shape per NPASS also runs with the device invariant checker on
 CHECKED = ("sweep033", "sweep100", "sweep193")
 #: the NPASS 4 shape that runs both repush rules
@@ -106,7 +106,7 @@ def test_builtin_kernels_match_oracle(name, layout):
         assert dev._eng.would_use_rows(len(weights)) == rows, batch
         got = dev.evaluate_builtin(family, weights)
         _same(got, builtin_oracle(w, family, weights, options.get("repush", "first")), (name, lid, batch))
-        if "check_invariants" in options:
+        if "check_invariants" in options and batch not in ds.ABORT_BATCHES:
             assert not got[:, 10].any(), (batch, got[:, 10])   # no INVARIANT row: the accounting held
 
 
