@@ -201,6 +201,7 @@ struct Slot {
 };
 
 class DeviceEngine {
+  friend class DeviceSuite;   // suite_host.hip.h: a program batch on several engines' traces in one launch
  public:
   DeviceEngine(py::dict d, int device, int n_slots = 4) : device_(device) {
     HIP_OK(hipSetDevice(device_));

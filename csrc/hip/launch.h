@@ -142,6 +142,23 @@ hipError_t launch_native_duo(int P, size_t lds, hipStream_t stream, const Builti
                              const fksd::RowNativeArgs& nat);
 int native_rows_waves_per_cu(size_t lds);
 int native_duo_blocks_per_cu(size_t lds);   // resident two-wave workgroups per CU
+// A trace suite's program batch in one grid of T * P two-wave workgroups
+// (replay_kernels.hip k_replay_native_duo_suite): block b replays program
+// b % P on trace order[b / P].  The workloads come from an HBM table, not from
+// the kernel arguments; fn / kc / koff of `nat` are indexed by the program
+// alone, so one copy of the batch's launch data serves every trace.
+struct SuiteArgs {
+  const DevWorkload* tab;     // [T] one entry per trace (heap_top set per launch layout)
+  const int32_t* order;       // [T] traces by descending pod count: the longest replays start first
+  int T, P;
+  const uint64_t* heap_off;   // [T] u64-word offset of trace t's heap area (P slices) inside gheap
+  DevResult* out;             // [T, P]
+  uint64_t* gheap;
+  double* table;              // [T, P, 13]
+};
+hipError_t launch_native_duo_suite(int blocks, size_t lds, hipStream_t stream, const SuiteArgs& s,
+                                   const fksd::RowNativeArgs& nat);
+int native_duo_suite_blocks_per_cu(size_t lds);
 // the resident program service (replay_kernels.hip k_native_service): its one
 // kernel argument, read back through the kernarg segment pointer
 struct ServiceArgs {

@@ -142,9 +142,11 @@ __global__ __launch_bounds__(64) void k_test_heap(const uint64_t* init, int n0, 
 }  // namespace
 
 #include "engine_host.hip.h"
+#include "suite_host.hip.h"
 
 namespace {
 using fks_host::DeviceEngine;
+using fks_host::DeviceSuite;
 
 py::array_t<uint64_t> test_wave_ops(py::array_t<uint64_t, py::array::c_style | py::array::forcecast> vals) {
   if (vals.size() != 64) throw std::invalid_argument("need 64 values");
@@ -565,6 +567,13 @@ PYBIND11_MODULE(_fks_hip, m) {
       .def("evaluate_native", &DeviceEngine::evaluate_native)
       .def("profile_native", &DeviceEngine::profile_native)
       .def("native_rt_table", &DeviceEngine::native_rt_table);
+  py::class_<DeviceSuite>(m, "DeviceSuite")
+      .def(py::init<py::list, int>(), py::arg("engines"), py::arg("n_slots") = 4)
+      .def("submit_native", &DeviceSuite::submit_native)
+      .def("ready", &DeviceSuite::ready)
+      .def("wait", &DeviceSuite::wait)
+      .def("n_slots", &DeviceSuite::n_slots)
+      .def("info", &DeviceSuite::info);
   py::class_<JitModule>(m, "JitModule")
       .def(py::init<py::bytes, py::array_t<uint64_t, py::array::c_style | py::array::forcecast>, int, int, bool>(),
            py::arg("image"), py::arg("rt"), py::arg("n_programs"), py::arg("device") = 0, py::arg("probe") = true)

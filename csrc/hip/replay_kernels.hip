@@ -531,6 +531,22 @@ __global__ __launch_bounds__(256) void k_gm_batch(int fn, const double* x, const
   out[i] = o;
   st[i] = s;
 }
+// A trace suite's program batch in one grid (launch.h SuiteArgs): block b
+// replays program b % P on trace order[b / P], two waves as k_replay_native_duo.
+// The workload is an entry of an HBM table, so kernarg_workload() has no
+// place here: the entry's address is made wave-uniform and read through the
+// constant address space (scalar loads, as the service's replay reads its
+// kernel arguments), for the hot scalars and the cold fields alike.
+__global__ __launch_bounds__(128, 1) void k_replay_native_duo_suite(fksk::SuiteArgs s, RowNativeArgs nat) {
+  const int g = (int)blockIdx.x / s.P;
+  const int p = (int)blockIdx.x - g * s.P;
+  const int t = uni(s.order[g]);
+  const fksd::DevWorkload* Wt = (const fksd::DevWorkload*)uniu64((uint64_t)(uintptr_t)(s.tab + t));
+  const FKS_CONST fksd::DevWorkload* Wc = const_ptr(Wt);
+  const fksd::DevWorkload& W = *(const fksd::DevWorkload*)Wc;
+  const uint64_t hoff = uniu64(const_ptr(s.heap_off)[t]);
+  replay_duo<false>(W, Wt, s.gheap + hoff, s.out + (size_t)t * s.P, nat, s.table + (size_t)t * s.P * 13, nullptr, p, p);
+}
 #endif
 
 template <int NPASS, bool GHEAP>
@@ -562,6 +578,7 @@ constexpr std::array<Row<fksk::BuiltinArgs, RowNativeArgs, int, uint32_t*, uint3
 constexpr std::array<Row<fksk::BuiltinArgs, RowNativeArgs>, 2> kNativeDuo = {
     {{0, k_replay_native_duo}, {1, k_replay_native_duo_prof}}};
 constexpr std::array<Row<fksk::ServiceArgs>, 1> kService = {{{0, k_native_service}}};
+constexpr std::array<Row<fksk::SuiteArgs, RowNativeArgs>, 1> kNativeDuoSuite = {{{0, k_replay_native_duo_suite}}};
 #endif
 #endif
 
@@ -655,6 +672,11 @@ hipError_t launch_native_service(int blocks, size_t lds, hipStream_t st, const S
 }
 int native_service_blocks_per_cu(size_t lds) { return blocks_per_cu(kService, 0, 128, lds); }
 int native_duo_blocks_per_cu(size_t lds) { return blocks_per_cu(kNativeDuo, 0, 128, lds); }
+hipError_t launch_native_duo_suite(int blocks, size_t lds, hipStream_t st, const SuiteArgs& s,
+                                   const fksd::RowNativeArgs& nat) {
+  return launch_row(kNativeDuoSuite, 0, dim3(blocks), dim3(128), lds, st, s, nat);
+}
+int native_duo_suite_blocks_per_cu(size_t lds) { return blocks_per_cu(kNativeDuoSuite, 0, 128, lds); }
 int native_rows_waves_per_cu(size_t lds) { return blocks_per_cu(kRowsNative, 0, 64, lds); }
 hipError_t native_rt_table(uint64_t* dev_out, hipStream_t s) {
   hipLaunchKernelGGL(k_native_rt_table, dim3(1), dim3(64), 0, s, dev_out);
@@ -670,7 +692,7 @@ template <>
 hipError_t unit_attrs<4, FKS_NPASS>(int mx) {
   hipError_t e = raise_lds(mx, kNative);
 #if FKS_NPASS == 1
-  if (e == hipSuccess) e = raise_lds(mx, kRowsNative, kNativeDuo);
+  if (e == hipSuccess) e = raise_lds(mx, kRowsNative, kNativeDuo, kNativeDuoSuite);
   // (the service kernel's static LDS -- the claim word -- counts against the 160 KiB too)
   if (e == hipSuccess) e = raise_lds(mx - 64, kService);
 #endif

@@ -589,7 +589,8 @@ class PendingPrograms:
 class SuiteEvaluator:
     """Batched exact evaluator bound to a trace suite (`core.traces.load_suite`).
 
-    A host-level layer over the existing engines: it adds no device code.
+    Families go through the existing engines, one launch per trace; program
+    batches through one fused device launch for the whole suite (`DeviceSuite`).
 
     ``evaluate_family`` / ``submit_family`` + ``wait`` return ``(tables, agg)``:
     the ``[T, P, 13]`` per-trace result tables and the ``[P, 4]`` suite
@@ -606,9 +607,19 @@ class SuiteEvaluator:
     ``evaluate_family`` is the synchronous form on slot 0: it raises while a
     ``submit_family(0, ...)`` batch is still in flight.
 
-    ``evaluate_programs`` is CPU-only for now: one ``Evaluator(device="cpu")``
-    per trace.  The device program path for suites (one JIT module, T
-    workloads) is not built yet.
+    ``evaluate_programs`` returns, per trace, the `EvalResult` of every
+    program text; ``score_programs`` the ``[T, P]`` scores and the same
+    ``[P, 4]`` aggregates; ``submit_programs`` + ``wait_programs`` are its
+    asynchronous form (slots of their own, not the family slots).  On an
+    MI355X whose traces all fit the <= 16-node row layout, each text is
+    compiled once and the batch runs as one grid of T * P two-wave workgroups
+    (`ops.hip_engine.DeviceSuite`: one JIT for the suite, the longest traces
+    first); rows the device declines or defers (UNSUPPORTED, BUDGET, TIMEOUT,
+    inexact) are re-scored on that trace's CPU VM and then the object engine,
+    so scores are the CPU backend's, and ``EvalResult.engine`` is
+    ``"hip-native"`` on the rows taken from the device.  A suite the fused
+    launch refuses, and the CPU backend, use one ``Evaluator(device="cpu")``
+    per trace.
 
     ``device``: as for `Evaluator`.
     """
@@ -647,6 +658,11 @@ class SuiteEvaluator:
         self._done: Dict[int, Tuple[np.ndarray, np.ndarray]] = {}   # CPU stand-in for in-flight slots
         self._in_flight: set = set()   # slots holding a submitted batch
         self._program_evaluators: Optional[List[Evaluator]] = None
+        self.n_slots = n_slots
+        self._device_suite = None      # hip_engine.DeviceSuite, built on first use (False: refused)
+        self._programs_in_flight: Dict[int, tuple] = {}   # program slot -> pending batch
+        self.stats = {"device_native": 0, "host": 0, "native_timeout": 0, "native_invariant": 0,
+                      "jit_s": 0.0, "jit_shapes": 0}
 
     def __len__(self) -> int:
         return len(self.suite)
@@ -709,11 +725,102 @@ class SuiteEvaluator:
         tables = np.stack([dev.wait(slot) for dev in self.devices])
         return tables, suite_aggregate(tables)
 
-    def evaluate_programs(self, codes: Sequence[str]) -> List[List[EvalResult]]:
-        """Per trace, the results of the program texts (CPU engines only)."""
+    def _bump(self, key: str, n=1) -> None:
+        self.stats[key] = self.stats.get(key, 0) + n
+
+    def _cpu_evaluators(self) -> List[Evaluator]:
         if self._program_evaluators is None:
             self._program_evaluators = [Evaluator(w, "cpu", dict(self.options), self.cpu_threads) for w in self.suite]
-        return [ev.evaluate_programs(list(codes)) for ev in self._program_evaluators]
+        return self._program_evaluators
+
+    @property
+    def device_suite(self):
+        """The suite's fused program launch (`hip_engine.DeviceSuite`), or None:
+        CPU backend, ``native`` / fault injection options, or a suite the device
+        path refuses (a trace off the <= 16-node row layout)."""
+        if self._device_suite is None:
+            self._device_suite = False
+            if (self.devices is not None and self.options.get("native", True)
+                    and not float(self.options.get("fault_rate", 0.0) or 0.0)):
+                from .ops import hip_engine
+                try:
+                    self._device_suite = hip_engine.DeviceSuite(self.devices, self.n_slots)
+                except ValueError:
+                    pass
+        return self._device_suite or None
+
+    def _submit_programs(self, slot: int, codes: List[str]) -> tuple:
+        ds = self.device_suite
+        if ds is None:
+            return (codes, None, None, [ev.evaluate_programs(codes) for ev in self._cpu_evaluators()])
+        compiled = [try_compile(c)[0] for c in codes]   # once per text, for every trace
+        dev_idx = [i for i, p in enumerate(compiled)
+                   if p is not None and p.device_ok and (ds.math_exact or not p.uses_libm)]
+        if dev_idx:
+            batch = ds.submit_native(slot, [compiled[i] for i in dev_idx])
+            self._bump("jit_s", batch.compile_s)
+            self._bump("jit_shapes", batch.compiled)
+        return (codes, compiled, dev_idx, None)
+
+    def _collect_programs(self, slot: int, pend: tuple) -> List[List[EvalResult]]:
+        codes, compiled, dev_idx, done = pend
+        if done is not None:
+            return done
+        T, n = len(self.suite), len(codes)
+        out: List[List[Optional[EvalResult]]] = [[None] * n for _ in range(T)]
+        if dev_idx:
+            tables = self.device_suite.wait(slot)
+            for t in range(T):
+                for row, i in zip(tables[t], dev_idx):
+                    if _native_deferred(row, self._bump):
+                        continue
+                    out[t][i] = _row_to_result(row, "hip-native")
+                    self._bump("device_native")
+        # what the device did not take: that trace's CPU VM, then the object engine
+        for t, ev in enumerate(self._cpu_evaluators()):
+            rest = [i for i in range(n) if out[t][i] is None]
+            if rest:
+                for i in rest:
+                    if compiled[i] is None:
+                        ev._bump("compile_errors", 1)
+                res = ev._evaluate_compiled([codes[i] for i in rest], [compiled[i] for i in rest], native=False)
+                for i, r in zip(rest, res):
+                    out[t][i] = r
+                self._bump("host", len(rest))
+        return out  # type: ignore[return-value]
+
+    def evaluate_programs(self, codes: Sequence[str]) -> List[List[EvalResult]]:
+        """Per trace, the results of the program texts.  Synchronous, on program slot 0."""
+        if 0 in self._programs_in_flight:
+            raise RuntimeError("suite program slot 0 busy: wait_programs() for its batch first")
+        return self._collect_programs(0, self._submit_programs(0, list(codes)))
+
+    @staticmethod
+    def _scores_of(results: List[List[EvalResult]]) -> Tuple[np.ndarray, np.ndarray]:
+        from .simulator.metrics import suite_aggregate_scores
+        scores = np.array([[r.score for r in row] for row in results], dtype=np.float64).reshape(len(results), -1)
+        raised = np.array([[r.exc != 0 for r in row] for row in results], dtype=bool).reshape(len(results), -1)
+        return np.where(raised, 0.0, scores), suite_aggregate_scores(scores, raised)
+
+    def score_programs(self, codes: Sequence[str]) -> Tuple[np.ndarray, np.ndarray]:
+        """(scores [T, P], agg [P, 4]) of the program texts: per-trace scores (a
+        raising replay scores 0) and `suite_aggregate`'s aggregates of them."""
+        return self._scores_of(self.evaluate_programs(codes))
+
+    def submit_programs(self, slot: int, codes: Sequence[str]) -> None:
+        """Start a program batch on program slot `slot` (on the device: one fused
+        launch on the `DeviceSuite`'s slot); `wait_programs(slot)` returns what
+        `score_programs` returns.  A slot still holding a batch raises."""
+        if slot in self._programs_in_flight:
+            raise RuntimeError(f"suite program slot {slot} busy: wait_programs() for its batch first")
+        if not 0 <= slot < self.n_slots:
+            raise IndexError(f"suite program slot {slot} outside [0, {self.n_slots})")
+        self._programs_in_flight[slot] = self._submit_programs(slot, list(codes))
+
+    def wait_programs(self, slot: int) -> Tuple[np.ndarray, np.ndarray]:
+        if slot not in self._programs_in_flight:
+            raise ValueError(f"suite program slot {slot} has no batch in flight")
+        return self._scores_of(self._collect_programs(slot, self._programs_in_flight.pop(slot)))
 
 
 _default: Dict[str, Evaluator] = {}

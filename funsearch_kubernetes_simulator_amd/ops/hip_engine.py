@@ -685,3 +685,103 @@ class DeviceEvaluator:
 
     def synchronize(self) -> None:
         self._eng.synchronize()
+
+
+class DeviceSuite:
+    """A trace suite's native program batches in one device launch each.
+
+    Built over the suite's `DeviceEvaluator` objects (one device, every trace
+    on the <= 16-node row layout): a batch of P programs becomes one grid of
+    T * P two-wave workgroups (`k_replay_native_duo_suite`), program p on
+    every trace, the longest traces first.  JIT-compiled code does not depend
+    on the workload, so the suite shares the first evaluator's compiler: each
+    shape is compiled once for all T traces.  Raises `ValueError` for a suite
+    the fused launch cannot take (the C++ side's gate)."""
+
+    def __init__(self, evaluators: Sequence[DeviceEvaluator], n_slots: int = 4):
+        self.evaluators = list(evaluators)
+        if not self.evaluators:
+            raise ValueError("a suite needs at least one trace")
+        self._eng = native().DeviceSuite([e._eng for e in self.evaluators], n_slots)
+        self.device = self.evaluators[0].device
+        #: device exp / log / pow == host libm (else programs using them stay on the host)
+        self.math_exact = all(e.math_exact for e in self.evaluators)
+        self._post: Dict[int, Tuple[int, np.ndarray]] = {}   # slot -> (P, native row indices)
+        self._mods: Dict[int, tuple] = {}                    # slot -> JIT modules of its batch in flight
+
+    def __len__(self) -> int:
+        return len(self.evaluators)
+
+    @property
+    def n_slots(self) -> int:
+        return self._eng.n_slots()
+
+    @property
+    def native_compiler(self):
+        return self.evaluators[0].native_compiler
+
+    def info(self) -> dict:
+        """T, the per-trace heap tops, LDS bytes and workgroups per CU of the last launch, its grid size."""
+        return dict(self._eng.info())
+
+    def prepare_native(self, progs: Sequence[CompiledPolicy]):
+        """JIT-compile and load the shapes `progs` need (`DeviceEvaluator.prepare_native`)."""
+        batch = self.native_compiler.prepare(progs)
+        if not self.math_exact:
+            for i, p in enumerate(progs):
+                if batch.ok[i] and p.uses_libm:
+                    batch.ok[i] = False
+                    batch.reasons[i] = "exp / log / pow: device math differs from this host's libm"
+        return batch
+
+    def release_native(self, batch) -> None:
+        self.native_compiler.release(batch.modules)
+
+    def submit_native(self, slot: int, progs: Sequence[CompiledPolicy], batch=None):
+        """Launch the programs the JIT accepted on every trace (one grid) on
+        `slot`; the others get EXC_UNSUPPORTED rows from `wait`, on every trace.
+        Returns the `NativeBatch`."""
+        if slot in self._post:
+            if batch is not None:
+                self.release_native(batch)
+            raise RuntimeError(f"suite slot {slot} busy: wait() for its batch first")
+        if batch is None:
+            batch = self.prepare_native(progs)
+        idx = np.flatnonzero(batch.ok)
+        try:
+            if idx.size:
+                self._eng.submit_native(slot, batch.fn[idx], batch.kc, batch.koff[idx])
+        except BaseException:
+            self.native_compiler.release(batch.modules)
+            raise
+        self._post[slot] = (len(progs), idx)
+        self._mods[slot] = batch.modules   # released once the batch is collected
+        return batch
+
+    def ready(self, slot: int) -> bool:
+        post = self._post.get(slot)
+        if post is not None and post[1].size == 0:
+            return True
+        return self._eng.ready(slot)
+
+    def wait(self, slot: int) -> np.ndarray:
+        """[T, P, 13] result tables of the batch in flight on `slot`."""
+        if slot not in self._post:
+            raise ValueError(f"suite slot {slot} has no batch in flight")
+        P, idx = self._post.pop(slot)
+        out = np.zeros((len(self.evaluators), P, len(RESULT_COLUMNS)))
+        out[:, :, 10] = 100.0   # EXC_UNSUPPORTED: not native -> the caller's next engine
+        try:
+            if idx.size:
+                out[:, idx] = self._eng.wait(slot)
+        finally:
+            mods = self._mods.pop(slot, None)
+            if mods:
+                self.native_compiler.release(mods)
+        return out
+
+    def evaluate_native(self, progs: Sequence[CompiledPolicy]) -> np.ndarray:
+        if not progs:
+            return np.zeros((len(self.evaluators), 0, len(RESULT_COLUMNS)))
+        self.submit_native(0, progs)
+        return self.wait(0)

@@ -71,9 +71,17 @@ def suite_aggregate(tables) -> "np.ndarray":
     import numpy as np
     from ..ops.cpu_engine import RESULT_COLUMNS
     tables = np.asarray(tables, dtype=np.float64)
-    P = tables.shape[1]
     raised = tables[:, :, RESULT_COLUMNS.index("exc")] != 0
-    scores = np.where(raised, 0.0, tables[:, :, RESULT_COLUMNS.index("score")])
+    return suite_aggregate_scores(tables[:, :, RESULT_COLUMNS.index("score")], raised)
+
+
+def suite_aggregate_scores(scores, raised) -> "np.ndarray":
+    """`suite_aggregate`'s rule on the ``[T, P]`` form: per-trace scores and a
+    mask of the (trace, policy) replays that raised -> ``[P, 4]``."""
+    import numpy as np
+    raised = np.asarray(raised, dtype=bool)
+    scores = np.where(raised, 0.0, np.asarray(scores, dtype=np.float64))
+    P = scores.shape[1]
     agg = np.zeros((P, 4))
     for p in range(P):
         agg[p, 0] = exact_mean(scores[:, p].tolist())
