@@ -875,6 +875,7 @@ class DeviceEngine {
     d["stack_bytes"] = (int64_t)stack_bytes_;
     d["row_flat"] = row_flat_;
     d["native_rows_last"] = last_native_rows_;
+    d["native_rows_top_last"] = last_native_top_;   // heap top of the last native-program row launch
     d["native_waves_last"] = last_native_waves_;
     d["native_duo_top_last"] = last_duo_top_;
     d["native_duo_per_cu_last"] = last_duo_per_cu_;   // resident programs per CU at that heap top
@@ -1291,9 +1292,13 @@ class DeviceEngine {
       last_native_waves_ = 2 * P;
       return;
     }
-    // largest heap top (2^k - 1 slots, at most the whole heap) that keeps two waves per CU
+    // largest heap top (2^k - 1 slots, at most the whole heap) that keeps two
+    // waves per CU, and no larger than the `row_heap_top` option
     int T = 1;
-    while (T < entries - 1 && rows_lds_bytes(W_.n_pods, 2 * T + 1, ra, true) <= kMaxLds / 2) T = 2 * T + 1;
+    while (T < entries - 1 && rows_lds_bytes(W_.n_pods, 2 * T + 1, ra, true) <= kMaxLds / 2 &&
+           (row_top_opt_ <= 0 || 2 * T + 1 <= row_top_opt_))
+      T = 2 * T + 1;
+    last_native_top_ = T;
     Wl.heap_top = T;
     const size_t lds = rows_lds_bytes(W_.n_pods, T, ra, true) + (profiled ? kRowProfBytes : 0);
     if (lds > kMaxLds) throw std::invalid_argument("native row kernel layout exceeds the 160 KiB LDS");
@@ -1366,7 +1371,7 @@ class DeviceEngine {
   int native_inflight_ = 0;    // programs kept in flight across slots (two-wave heap-top sizing)
   int native_duo_top_ = -1;    // forced two-wave heap top (-1: auto)
   int last_duo_top_ = 0, last_duo_per_cu_ = 0;
-  int last_native_rows_ = 0, last_native_waves_ = 0;
+  int last_native_rows_ = 0, last_native_waves_ = 0, last_native_top_ = 0;
   size_t row_min_lds_ = 0;
   int32_t max_class_pods_ = 0;   // most GPU pods of one gpu_milli class (row kernel: < 2^16)
   int32_t max_gpu_milli_ = 0;    // largest per-GPU milli total (row kernel: < 2^16)

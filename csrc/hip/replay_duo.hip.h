@@ -56,7 +56,7 @@ struct DuoBox {
 constexpr int kDuoNodeInts = 16;   // cpu_left, mem_left, gpu_left, -, gml[8], wcnt[4]
 constexpr size_t kDuoSBytes = (size_t)kRow * kDuoNodeInts * 4 + (size_t)kRow * 32;
 __host__ __device__ inline size_t duo_lds_bytes(int n_pods, int T) {
-  return rows_lds_bytes(n_pods, T, 1, true) + ((sizeof(DuoBox) + 15) & ~size_t(15)) + kDuoSBytes;
+  return rows_lds_bytes(n_pods, T, 1, true, true) + ((sizeof(DuoBox) + 15) & ~size_t(15)) + kDuoSBytes;
 }
 
 __device__ __forceinline__ uint32_t duo_ld(FKS_LDS uint32_t* p) {
@@ -272,8 +272,8 @@ __device__ void replay_duo(const DevWorkload& W, const DevWorkload* Wdev, uint64
   FKS_LDS int32_t* cls_lds = reinterpret_cast<FKS_LDS int32_t*>(lds + kRowsPerWave * kWeights);
   FKS_LDS char* rowbase = reinterpret_cast<FKS_LDS char*>(lds + kRowsPerWave * kWeights) + kRowClassBytes;
   FKS_LDS int32_t* ntab = cls_lds + kRow * kRowClassSlots;
-  FKS_LDS int64_t* kcp = reinterpret_cast<FKS_LDS int64_t*>(rowbase + rows_row_bytes(N, T));
-  FKS_LDS DuoBox* box = reinterpret_cast<FKS_LDS DuoBox*>(reinterpret_cast<FKS_LDS char*>(lds) + rows_lds_bytes(N, T, 1, true));
+  FKS_LDS int64_t* kcp = reinterpret_cast<FKS_LDS int64_t*>(rowbase + rows_row_bytes(N, T, true));
+  FKS_LDS DuoBox* box = reinterpret_cast<FKS_LDS DuoBox*>(reinterpret_cast<FKS_LDS char*>(lds) + rows_lds_bytes(N, T, 1, true, true));
   FKS_LDS int32_t* sstate = reinterpret_cast<FKS_LDS int32_t*>(reinterpret_cast<FKS_LDS char*>(box) +
                                                                 ((sizeof(DuoBox) + 15) & ~size_t(15)));
   FKS_LDS uint64_t* sacc = reinterpret_cast<FKS_LDS uint64_t*>(sstate + kRow * kDuoNodeInts);

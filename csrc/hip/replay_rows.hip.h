@@ -16,6 +16,10 @@
 //     under the current path end (15 child pairs, one per lane) per round, a
 //     push gathers all 16 ancestors at once; the top 2^k-1 slots of each heap
 //     sit in LDS, the rest in the policy's HBM slice;
+//   * a failed placement finds its anchor -- the first pending deletion in
+//     array order -- by scanning the keys, 32 slots per step (one pair per
+//     lane); no deletion bitmap is kept, so heap stores carry no marking and
+//     the row's LDS holds a heap level more;
 //   * divergence between the four policies (deletion vs creation, placement vs
 //     failure) is ordinary exec masking: every branch condition is
 //     row-uniform, so a row is always wholly active or wholly masked.
@@ -104,12 +108,20 @@ __device__ __forceinline__ int row_read(int v, int rbase, int k) {
 typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
 
 // ---- one policy's heap, driven by the 16 lanes of its row ---------------------
-template <bool FLAT = FKS_ROW_FLAT != 0>
+// MAP: keep an LDS bitmap of the slots that hold a DELETION (one masked-OR
+// atomic per heap store) and answer first_deletion() from it: the two-wave
+// kernels (replay_duo.hip.h).  The row kernels run MAP = false: no bitmap, no
+// LDS for it, and scan_deletion() reads the keys themselves -- the first
+// deletion sits just behind the waiting retries at the top of the heap (within
+// the first 32 slots for 93 % of the OpenB trace's failed placements, always
+// below 512), so the scan costs about what the bitmap's did and every heap
+// store is free of the marking.
+template <bool FLAT = FKS_ROW_FLAT != 0, bool MAP = true>
 struct RowHeapT {
   FKS_GLOBAL uint64_t* h;     // HBM slice (address = slot + 1)
   FKS_LDS uint64_t* top;      // LDS copy of addresses [0, T + 1)
   int T;                      // slots [0, T) in LDS, T = 2^k - 1
-  FKS_LDS uint32_t* delmap;   // bit p set <=> slot p holds a deletion
+  FKS_LDS uint32_t* delmap;   // MAP: bit p set <=> slot p holds a deletion (unset and unused otherwise)
   int lb;
   int j, rbase;               // lane within the row, first lane of the row
   uint32_t anc, dir;          // subtree node j: BFS indices of its ancestors / of those stepping right
@@ -150,6 +162,7 @@ struct RowHeapT {
   // hit the same word in one instruction.  LDS operations of a wave complete
   // in order, so later bitmap reads see it without an extra wait.
   __device__ __forceinline__ void mark(int pos, uint64_t v) const {
+    if constexpr (!MAP) return;
     const uint32_t bit = 1u << (pos & 31);
     const uint32_t data = (v & 3) == kDelKind ? bit : 0u;
     const uint32_t addr = (uint32_t)(uintptr_t)(delmap + (pos >> 5));
@@ -230,8 +243,9 @@ struct RowHeapT {
     if (j == 0) { st(aJ, item); mark(aJ, item); }
   }
 
-  // index of the first DELETION in slots [0, n), or -1
+  // index of the first DELETION in slots [0, n), or -1: from the bitmap
   __device__ int first_deletion(int n) const {
+    static_assert(MAP, "bitmap-free heaps scan the keys: scan_deletion");
     const int words = (n + 31) >> 5;
     for (int base = 0; base < words; base += kRow) {
       const int wi = base + j;
@@ -242,6 +256,41 @@ struct RowHeapT {
         const int fl = __ffs(b) - 1;
         const uint32_t fw = (uint32_t)row_read((int)w, rbase, fl);
         return ((base + fl) << 5) + (__ffs(fw) - 1);
+      }
+    }
+    return -1;
+  }
+
+  // The same answer from the keys, in array order, 32 slots per step: lane j
+  // reads the aligned pair at addresses base + 2j, base + 2j + 1 (slots
+  // base + 2j - 1 and base + 2j; address 0 is padding, and a pair never
+  // straddles T), the row takes the first hit in lane order, low half before
+  // high half, and stops at the first step with one.  `key` receives the
+  // entry found (the hit lane hands it to the row), so the caller needs no
+  // dependent load.  With no deletion pending the scan runs to n and returns
+  // -1: n / 32 steps per failure, which needs a pod that fits nowhere (built-in
+  // families score every feasible node >= 1) or a program scoring <= 0
+  // everywhere -- over a shrinking heap, about one ordinary replay in total,
+  // so no counter bounds it.
+  __device__ int scan_deletion(int n, uint64_t& key) const {
+    // the step at base = 32 i covers slots [base - 1, base + 31): slot n - 1 of
+    // a heap of n = base entries opens a step of its own, so the steps run
+    // while base - 1 < n -- on this lane's slots c = base + 2j - 1 and c + 1
+    // (c odd; -1: the padding), while c < n + 2j
+    const int lim = n + 2 * j;
+    for (int c = 2 * j - 1; c < lim; c += 2 * kRow) {
+      u64x2 pr = {0, 0};
+      if (c < n) pr = ld_pair(c);       // (c + 1 <= n <= N: inside the heap's allocation)
+      const bool d0 = c >= 0 && c < n && ((uint32_t)pr.x & 3u) == (uint32_t)kDelKind;
+      const bool d1 = c + 1 < n && ((uint32_t)pr.y & 3u) == (uint32_t)kDelKind;
+      const uint32_t b0 = row_ballot(d0, rbase);
+      const uint32_t b = b0 | row_ballot(d1, rbase);
+      if (b) {
+        const int fl = __ffs(b) - 1;
+        const uint64_t mine = d0 ? pr.x : pr.y;
+        key = ((uint64_t)(uint32_t)row_read((int)(mine >> 32), rbase, fl) << 32) |
+              (uint32_t)row_read((int)(uint32_t)mine, rbase, fl);
+        return c - 2 * j + 1 + 2 * fl - (int)((b0 >> fl) & 1u);
       }
     }
     return -1;
@@ -344,7 +393,7 @@ struct RowAcc {
 
 // LDS per wave: [4 x 16 weights | 64 class values | 16 x 4 node constants |
 // 16 x 3 node reciprocals | 10 GPU-capacity reciprocals] then per row
-// [deletion bitmap | heap top].
+// [heap top | cold state] (the two-wave kernels' row: a deletion bitmap first).
 constexpr int kNodeConsts = 4;   // cpu_total, mem_total, ngpus, per-GPU milli total
 constexpr int kNodeRecips = 6;   // DevWorkload::node_recip (3), then the same divisors as doubles
 constexpr int kCapRecips = 10;   // DevWorkload::cap_recip (9) + pad
@@ -405,17 +454,19 @@ __device__ __forceinline__ void fill_node_tables(const DevWorkload& W, FKS_LDS i
   }
   if (lane <= kGmax) row_cap_recips(ntab)[lane] = W.cap_recip[lane];
 }
-// per row: deletion bitmap | heap top (T + 1 slots) | cold state (trace hash,
-// snapshot threshold beyond the host's schedule: read rarely, so kept out of
-// the registers the 4- and 5-waves-per-SIMD register budgets are tight on)
+// per row: heap top (T + 1 slots) | cold state (trace hash, snapshot threshold
+// beyond the host's schedule: read rarely, so kept out of the registers the
+// 4- and 5-waves-per-SIMD register budgets are tight on); map: the deletion
+// bitmap of RowHeapT<.., MAP = true> in front (the two-wave kernels)
 constexpr int kRowColdBytes = 32;   // hash, threshold, repush / dropped / snapshot counters
-__host__ __device__ inline size_t rows_row_bytes(int n_pods, int T) {
-  return (size_t)lds_delmap_words(n_pods) * 4 + (size_t)(T + 1) * 8 + kRowColdBytes;
+__host__ __device__ inline size_t rows_row_bytes(int n_pods, int T, bool map = false) {
+  return (map ? (size_t)lds_delmap_words(n_pods) * 4 : 0) + (size_t)(T + 1) * 8 + kRowColdBytes;
 }
 // native programs (kc = true) also stage each active row's constant block
 // (kKcLds int64) after the rows' heap areas
-__host__ __device__ inline size_t rows_lds_bytes(int n_pods, int T, int rows = kRowsPerWave, bool kc = false) {
-  return (size_t)kRowsPerWave * kWeights * 8 + kRowClassBytes + (size_t)rows * rows_row_bytes(n_pods, T) +
+__host__ __device__ inline size_t rows_lds_bytes(int n_pods, int T, int rows = kRowsPerWave, bool kc = false,
+                                                 bool map = false) {
+  return (size_t)kRowsPerWave * kWeights * 8 + kRowClassBytes + (size_t)rows * rows_row_bytes(n_pods, T, map) +
          (kc ? (size_t)rows * kKcLds * 8 : 0);
 }
 
@@ -569,9 +620,8 @@ __device__ void replay_rows(const DevWorkload& W, const DevWorkload* Wdev, const
   // registers through the pop
   FKS_LDS int32_t* ntab = cls_lds + kRow * kRowClassSlots;
   fill_node_tables(W, ntab, lane);
-  RowHeapT<FLAT> heap;
-  heap.delmap = reinterpret_cast<FKS_LDS uint32_t*>(rowbase);
-  heap.top = reinterpret_cast<FKS_LDS uint64_t*>(rowbase + (size_t)lds_delmap_words(N) * 4);
+  RowHeapT<FLAT, false> heap;   // no deletion bitmap: scan_deletion
+  heap.top = reinterpret_cast<FKS_LDS uint64_t*>(rowbase);
   heap.h = global_ptr(gheap + (size_t)slot * row_heap_entries(N));
   heap.bind();
   heap.T = T;
@@ -627,7 +677,7 @@ __device__ void replay_rows(const DevWorkload& W, const DevWorkload* Wdev, const
       reinterpret_cast<FKS_LDS char*>(lds + kRowsPerWave * kWeights) + kRowClassBytes +
       (size_t)ra * rows_row_bytes(N, T)) + (size_t)row * kKcLds;
 
-  // start policy p on this row: weights, heap image, bitmap, node state, counters
+  // start policy p on this row: weights, heap image, node state, counters
   auto begin = [&]() {
     if constexpr (kNative) {
       const uint64_t fne = *global_ptr(&nat.fn[p]);
@@ -652,7 +702,6 @@ __device__ void replay_rows(const DevWorkload& W, const DevWorkload* Wdev, const
         else *reinterpret_cast<FKS_GLOBAL u64x2*>(heap.h + 2 * i) = v;
       }
     }
-    for (int i = jv; i < lds_delmap_words(N); i += kRow) heap.delmap[i] = 0u;
     const FKS_CONST DevWorkload* Wb = cold_ptr(Wdev);
     nr.cpu_left[0] = Wb->cpu_left0[jv];
     nr.mem_left[0] = Wb->mem_left0[jv];
@@ -809,9 +858,10 @@ __device__ void replay_rows(const DevWorkload& W, const DevWorkload* Wdev, const
             acc.stash_unit(frag, jv);
           }
           acc.add_stash(jv);
-          const int f = heap.first_deletion(n);
+          uint64_t anchor = 0;
+          const int f = heap.scan_deletion(n, anchor);
           if (f >= 0) {
-            const uint64_t nt = (heap.ld(f) >> tshift) + 1;
+            const uint64_t nt = (anchor >> tshift) + 1;
             if (nt > time_max) { exc = EXC_UNSUPPORTED; break; }
             push_item = (nt << tshift) | ((uint64_t)rank << lb) | kRetry;
             bump(0);
