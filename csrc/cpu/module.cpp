@@ -359,6 +359,16 @@ PYBIND11_MODULE(_fks_cpu, m) {
     FixedAcc a; for (double x : xs) a.add(x);
     return py::make_tuple(fixed_mean(a), a.inexact);
   });
+  // the accumulator and the division on their own (tests/test_exact_arith_cases.py):
+  // the sum * 2^96 as the two's-complement words (lo, hi), and A = hi << 64 | lo
+  m.def("exact_acc", [](std::vector<double> xs) {
+    FixedAcc a; for (double x : xs) a.add(x);
+    const u128 s = (u128)a.sum;
+    return py::make_tuple((uint64_t)s, (uint64_t)(s >> 64), a.count, a.inexact);
+  });
+  m.def("fixed_div_round", [](uint64_t lo, uint64_t hi, uint64_t n) {
+    return fixed_div_round((i128)(((u128)hi << 64) | lo), n);
+  });
 
   // ---- baseline program JIT (csrc/jit): bytecode -> gfx950 machine code
   m.def("gcn_compile", [](py::bytes code, py::array_t<uint8_t, py::array::c_style | py::array::forcecast> ctag,

@@ -142,40 +142,11 @@ __device__ __forceinline__ int first_lane(uint64_t m) { return __ffsll((unsigned
 using i128 = __int128;
 using u128 = unsigned __int128;
 
-struct FixedAccD {
-  i128 sum;
-  int64_t count;
-  int32_t inexact;
-  __device__ void init() { sum = 0; count = 0; inexact = 0; }
-  // v is wave-uniform; all lanes do the same (scalarised) work.
-  __device__ void add(double v) {
-    ++count;
-    uint64_t bits = (uint64_t)__double_as_longlong(v);
-    int E = (int)((bits >> 52) & 0x7FF);
-    uint64_t frac = bits & ((1ull << 52) - 1);
-    if (E == 0 && frac == 0) return;
-    if (E == 0x7FF || E == 0) { inexact = 1; return; }  // inf/nan, subnormal
-    uint64_t M = frac | (1ull << 52);
-    int shift = E - 979;  // v * 2^96 = M * 2^(E-1075+96)
-    if (shift < 0) {
-      if (shift <= -53 || (M & ((1ull << (-shift)) - 1))) { inexact = 1; return; }
-      M >>= (-shift);
-      shift = 0;
-    }
-    if (shift > 126 - 53) { inexact = 1; return; }
-    i128 t = (i128)(u128)M << shift;
-    if (bits >> 63) t = -t;
-    sum += t;
-    u128 mag = sum < 0 ? (u128)(-sum) : (u128)sum;
-    if (mag >> 126) inexact = 1;
-  }
-};
-
 // The replay's five exact accumulators (4 utilisation means + fragmentation)
 // spread over lanes: accumulator k lives in lane k, so the whole set costs a
 // handful of VGPRs instead of ~35 loop-carried SGPRs (which the compiler
 // would otherwise spill through v_writelane / v_readlane on every event).
-// Same arithmetic as FixedAccD.
+// Same arithmetic and `inexact` contract as the host twin's fks::FixedAcc.
 struct LaneAcc {
   i128 sum;
   int64_t count;

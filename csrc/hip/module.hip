@@ -139,6 +139,85 @@ __global__ __launch_bounds__(64) void k_test_heap(const uint64_t* init, int n0, 
   }
 }
 
+// ---- exact-arithmetic self-tests (tests/test_gpu_exact_arith.py) -------------------
+// The production accumulators, division and finalisers, unchanged, on inputs
+// no replay forms.  One wave per block.
+//
+// Block g runs five sequences through LaneAcc::add, one per accumulator k:
+// vals[offs[5g + k], offs[5g + k + 1]); lane k reports (lo, hi, count, inexact).
+__global__ __launch_bounds__(64) void k_test_lane_acc(const double* vals, const int32_t* offs, uint64_t* out) {
+  const int g = blockIdx.x, lane = lane_id();
+  LaneAcc acc;
+  acc.init();
+  for (int k = 0; k < 5; ++k) {
+    const int b = offs[5 * g + k], e = offs[5 * g + k + 1];
+    for (int i = b; i < e; ++i) acc.add(k, vals[i]);   // (block-uniform index: v is wave-uniform)
+  }
+  if (lane < 5) {
+    uint64_t* o = out + (size_t)(5 * g + lane) * 4;
+    o[0] = (uint64_t)(u128)acc.sum;
+    o[1] = (uint64_t)((u128)acc.sum >> 64);
+    o[2] = (uint64_t)acc.count;
+    o[3] = (uint64_t)(uint32_t)acc.inexact;
+  }
+}
+
+// Row slot s = 4 * block + row runs its own program ops[offs[s], offs[s + 1])
+// on a RowAcc (optionally started from the injected state of lanes 0-4), every
+// lane of the row reports its raw (lo, hi, count, inexact), and the row then
+// finishes like a replay: write_row_result with the slot's meta
+// (processed, exc, n_repush, n_dropped, hash) into res[s] and table row s.
+enum { kTestAdd = 0, kTestAddUnit = 1, kTestStashUnit = 2, kTestAddStash = 3, kTestStashDrop = 4 };
+__global__ __launch_bounds__(64) void k_test_row_acc(const int32_t* ops, const double* vals, const int32_t* offs,
+                                                      const uint64_t* inject, const int64_t* meta, int S, uint64_t* raw,
+                                                      DevResult* res, double* table) {
+  const int lane = lane_id(), jv = lane & 15, rbase = lane & 48;
+  const int s = blockIdx.x * kRowsPerWave + (lane >> 4);
+  if (s >= S) return;   // whole rows leave
+  RowAcc acc;
+  acc.init();
+  if (inject && jv < 5) {
+    const uint64_t* q = inject + ((size_t)s * 5 + jv) * 4;
+    acc.lo = q[0];
+    acc.hi = q[1];
+    acc.count = (int32_t)q[2];
+    acc.inexact = (int32_t)q[3];
+  }
+  const int b = offs[s], e = offs[s + 1];
+  for (int i = b; i < e; ++i) {   // row-uniform trip count and operands
+    const int op = ops[i] & 0xFF, k = ops[i] >> 8;
+    const double v = vals[i];
+    if (op == kTestAdd) acc.add(k, v, jv);
+    else if (op == kTestAddUnit) acc.add_unit(k, v, jv);
+    else if (op == kTestStashUnit) acc.stash_unit(v, jv);
+    else if (op == kTestAddStash) acc.add_stash(jv);
+    else acc.stash_drop();
+  }
+  uint64_t* o = raw + ((size_t)s * kRow + jv) * 4;
+  o[0] = acc.lo;
+  o[1] = acc.hi;
+  o[2] = (uint64_t)(int64_t)acc.count;
+  o[3] = (uint64_t)(uint32_t)acc.inexact;
+  const int64_t* m = meta + (size_t)s * 5;
+  write_row_result(acc, jv, rbase, (int32_t)m[0], (int32_t)m[1], m[2], (int)m[3], (uint64_t)m[4], res + s,
+                   table + (size_t)s * 13);
+}
+
+// fixed_div_round_dev(A, n), A = (hi << 64 | lo) as a signed 128-bit word: one pair per lane
+__global__ __launch_bounds__(64) void k_test_fixed_div(const uint64_t* lo, const uint64_t* hi, const uint64_t* n,
+                                                        double* out, int64_t N) {
+  const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (i >= N) return;
+  out[i] = fixed_div_round_dev((i128)(((u128)hi[i] << 64) | lo[i]), n[i]);
+}
+
+// div_by_recip(n, d, z) for the integers n in [start, start + count)
+__global__ __launch_bounds__(256) void k_test_div_by_recip(double d, double z, int64_t start, int64_t count, double* out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= count) return;
+  out[i] = div_by_recip((double)(start + i), d, z);
+}
+
 }  // namespace
 
 #include "engine_host.hip.h"
@@ -272,6 +351,146 @@ py::tuple test_heap(py::array_t<uint64_t, py::array::c_style | py::array::forcec
   HIP_OK(hipMemcpy(popped.mutable_data(), dpop, (size_t)(nops + 2) * 8, hipMemcpyDeviceToHost));
   for (void* p : {(void*)di, (void*)dops, (void*)dout, (void*)dpop, (void*)dn}) (void)hipFree(p);
   return py::make_tuple(out, popped);
+}
+
+// ---- exact-arithmetic self-tests: host side -----------------------------------------
+// device buffer of the self-tests: uploaded (or filled with `fill`) on
+// construction, freed on scope exit
+struct TestBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+  TestBuf(size_t n, const void* src = nullptr, int fill = 0) : bytes(n) {
+    HIP_OK(hipMalloc(&p, n ? n : 16));
+    if (src && n) HIP_OK(hipMemcpy(p, src, n, hipMemcpyHostToDevice));
+    else HIP_OK(hipMemset(p, fill, n ? n : 16));
+  }
+  TestBuf(const TestBuf&) = delete;
+  TestBuf& operator=(const TestBuf&) = delete;
+  ~TestBuf() { (void)hipFree(p); }
+  template <class T> T* as() const { return reinterpret_cast<T*>(p); }
+  void download(void* dst) const { if (bytes) HIP_OK(hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost)); }
+};
+using ArrF64 = py::array_t<double, py::array::c_style | py::array::forcecast>;
+using ArrI32 = py::array_t<int32_t, py::array::c_style | py::array::forcecast>;
+using ArrI64 = py::array_t<int64_t, py::array::c_style | py::array::forcecast>;
+using ArrU64 = py::array_t<uint64_t, py::array::c_style | py::array::forcecast>;
+
+// offs: n + 1 non-decreasing offsets into an array of `total` entries, from 0 to total
+void check_offsets(const ArrI32& offs, int64_t n, int64_t total) {
+  if ((int64_t)offs.size() != n + 1) throw std::invalid_argument("offsets: need one more than sequences");
+  const int32_t* o = offs.data();
+  if (o[0] != 0 || o[n] != total) throw std::invalid_argument("offsets: must span the values");
+  for (int64_t i = 0; i < n; ++i)
+    if (o[i] > o[i + 1]) throw std::invalid_argument("offsets: decreasing");
+}
+
+// LaneAcc::add on 5 * G sequences (k_test_lane_acc): uint64 [5 * G, 4] = (lo, hi, count, inexact)
+py::array_t<uint64_t> test_lane_acc(ArrF64 vals, ArrI32 offs) {
+  const int64_t nseq = (int64_t)offs.size() - 1;
+  if (nseq < 5 || nseq % 5) throw std::invalid_argument("lane acc: sequences come in fives");
+  check_offsets(offs, nseq, (int64_t)vals.size());
+  TestBuf dv((size_t)vals.size() * 8, vals.data()), doff((size_t)offs.size() * 4, offs.data());
+  TestBuf dout((size_t)nseq * 4 * 8, nullptr, 0xFF);
+  hipLaunchKernelGGL(k_test_lane_acc, dim3((unsigned)(nseq / 5)), dim3(64), 0, 0, dv.as<double>(), doff.as<int32_t>(),
+                     dout.as<uint64_t>());
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipDeviceSynchronize());
+  py::array_t<uint64_t> out({(py::ssize_t)nseq, (py::ssize_t)4});
+  dout.download(out.mutable_data());
+  return out;
+}
+
+// Row programs (k_test_row_acc) and both finalisers on their results:
+// ops int32 (op | k << 8), vals, offs [S + 1]; inject uint64 [S, 5, 4] or
+// empty; meta int64 [S, 5] = (processed, exc, n_repush, n_dropped, hash).
+// Returns (raw uint64 [S, 16, 4], acc uint64 [S, 2, 5] (lo, hi), fields int64
+// [S, 9] = (n_events, n_snap, n_frag, n_unplaced, n_repush, max_nodes, hash,
+// exc, inexact) of the DevResults, write_row_result's table [S, 13],
+// k_eval_reduce's table [S, 13] of those DevResults).
+py::tuple test_row_acc(ArrI32 ops, ArrF64 vals, ArrI32 offs, ArrU64 inject, ArrI64 meta) {
+  const int64_t S = (int64_t)offs.size() - 1;
+  if (S < 1 || S > (1 << 20)) throw std::invalid_argument("row acc: 1 .. 2^20 row slots");
+  if (ops.size() != vals.size()) throw std::invalid_argument("row acc: ops and vals differ in length");
+  check_offsets(offs, S, (int64_t)ops.size());
+  for (py::ssize_t i = 0; i < ops.size(); ++i) {
+    const int32_t op = ops.data()[i] & 0xFF, k = ops.data()[i] >> 8;
+    if (op > kTestStashDrop || k < 0 || k > 4) throw std::invalid_argument("row acc: bad op");
+  }
+  if (inject.size() != 0 && inject.size() != S * 20) throw std::invalid_argument("row acc: inject must be [S, 5, 4]");
+  if (meta.size() != S * 5) throw std::invalid_argument("row acc: meta must be [S, 5]");
+  TestBuf dops((size_t)ops.size() * 4, ops.data()), dv((size_t)vals.size() * 8, vals.data());
+  TestBuf doff((size_t)offs.size() * 4, offs.data()), dinj((size_t)inject.size() * 8, inject.data());
+  TestBuf dmeta((size_t)meta.size() * 8, meta.data());
+  TestBuf draw((size_t)S * kRow * 4 * 8, nullptr, 0xFF), dres((size_t)S * sizeof(DevResult), nullptr, 0xFF);
+  TestBuf dt1((size_t)S * 13 * 8, nullptr, 0xFF), dt2((size_t)S * 13 * 8, nullptr, 0xFF);
+  hipLaunchKernelGGL(k_test_row_acc, dim3((unsigned)((S + kRowsPerWave - 1) / kRowsPerWave)), dim3(64), 0, 0,
+                     dops.as<int32_t>(), dv.as<double>(), doff.as<int32_t>(),
+                     inject.size() ? dinj.as<uint64_t>() : nullptr, dmeta.as<int64_t>(), (int)S, draw.as<uint64_t>(),
+                     dres.as<DevResult>(), dt1.as<double>());
+  HIP_OK(hipGetLastError());
+  hipLaunchKernelGGL(k_eval_reduce, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, 0, dres.as<DevResult>(),
+                     dt2.as<double>(), (int)S);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipDeviceSynchronize());
+  py::array_t<uint64_t> raw({(py::ssize_t)S, (py::ssize_t)kRow, (py::ssize_t)4});
+  py::array_t<uint64_t> acc({(py::ssize_t)S, (py::ssize_t)2, (py::ssize_t)5});
+  py::array_t<int64_t> fields({(py::ssize_t)S, (py::ssize_t)9});
+  py::array_t<double> t1({(py::ssize_t)S, (py::ssize_t)13}), t2({(py::ssize_t)S, (py::ssize_t)13});
+  std::vector<DevResult> res((size_t)S);
+  draw.download(raw.mutable_data());
+  dres.download(res.data());
+  dt1.download(t1.mutable_data());
+  dt2.download(t2.mutable_data());
+  for (int64_t s = 0; s < S; ++s) {
+    const DevResult& r = res[(size_t)s];
+    for (int k = 0; k < 5; ++k) {
+      acc.mutable_data()[s * 10 + k] = r.acc_lo[k];
+      acc.mutable_data()[s * 10 + 5 + k] = r.acc_hi[k];
+    }
+    const int64_t f[9] = {r.n_events, r.n_snap, r.n_frag, r.n_unplaced, r.n_repush, r.max_nodes, (int64_t)r.hash,
+                          r.exc, r.inexact};
+    std::memcpy(fields.mutable_data() + s * 9, f, sizeof(f));
+  }
+  return py::make_tuple(raw, acc, fields, t1, t2);
+}
+
+// fixed_div_round_dev on (lo, hi, n) triples (k_test_fixed_div)
+py::array_t<double> test_fixed_div(ArrU64 lo, ArrU64 hi, ArrU64 n) {
+  const int64_t N = (int64_t)lo.size();
+  if ((int64_t)hi.size() != N || (int64_t)n.size() != N) throw std::invalid_argument("fixed div: lengths differ");
+  py::array_t<double> out(N);
+  if (N == 0) return out;
+  TestBuf dlo((size_t)N * 8, lo.data()), dhi((size_t)N * 8, hi.data()), dn((size_t)N * 8, n.data());
+  TestBuf dout((size_t)N * 8, nullptr, 0xFF);
+  hipLaunchKernelGGL(k_test_fixed_div, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, 0, dlo.as<uint64_t>(),
+                     dhi.as<uint64_t>(), dn.as<uint64_t>(), dout.as<double>(), N);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipDeviceSynchronize());
+  dout.download(out.mutable_data());
+  return out;
+}
+
+// The reciprocal division of divisor d, as the engine sets it up: z =
+// fks_recip_verified(d, hi) (0.0: not verified, the kernels divide), and
+// div_by_recip(n, d, RN(1 / d)) on the host and on the device for the integers
+// n in [start, start + count) within [0, hi].  Returns (z, host, device).
+py::tuple test_div_by_recip(int64_t d, int64_t hi, int64_t start, int64_t count) {
+  if (d < 1 || hi < 0 || hi >= (int64_t(1) << 31)) throw std::invalid_argument("div_by_recip: d >= 1, 0 <= hi < 2^31");
+  if (count < 0) count = hi + 1 - start;
+  if (start < 0 || count < 1 || start + count > hi + 1) throw std::invalid_argument("div_by_recip: range outside [0, hi]");
+  std::vector<std::pair<std::pair<int64_t, int64_t>, double>> cache;
+  const double z = fks_host::fks_recip_verified(d, hi, cache);
+  const double dd = (double)d, zz = 1.0 / dd;
+  py::array_t<double> host(count), dev(count);
+  double* h = host.mutable_data();
+  for (int64_t i = 0; i < count; ++i) h[i] = div_by_recip((double)(start + i), dd, zz);
+  TestBuf dout((size_t)count * 8, nullptr, 0xFF);
+  hipLaunchKernelGGL(k_test_div_by_recip, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, 0, dd, zz, start, count,
+                     dout.as<double>());
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipDeviceSynchronize());
+  dout.download(dev.mutable_data());
+  return py::make_tuple(z, host, dev);
 }
 
 // Loader state shared by every JIT module of a device: a private
@@ -418,60 +637,95 @@ class JitModule {
 // `n` arguments per function drawn to cover every branch of exp / log / pow
 // (tiny, near 1, large, subnormal results, over- / underflow).  Returns the
 // mismatch count per function and the first few mismatching arguments.
-py::dict glibc_math_selfcheck(int64_t n, uint64_t seed) {
+//
+// The arguments of that draw, `n` per function (glibc_math_selfcheck_args
+// hands the same ones to the device test: tests/test_gpu_glibc_math.py).
+struct GmArgs {
+  std::vector<double> exp_x, log_x, pow_x, pow_y;
+};
+GmArgs glibc_math_args(int64_t n, uint64_t seed) {
   std::mt19937_64 rng(seed);
   std::uniform_real_distribution<double> U(0.0, 1.0);
   auto bits = [&](uint64_t lo_exp, uint64_t hi_exp) {
     const uint64_t e = lo_exp + rng() % (hi_exp - lo_exp + 1);
     return fksd::gm::asd((e << 52) | (rng() & ((1ull << 52) - 1)));
   };
+  GmArgs a;
+  const size_t cap = (size_t)(n > 0 ? n : 0);
+  a.exp_x.reserve(cap); a.log_x.reserve(cap); a.pow_x.reserve(cap); a.pow_y.reserve(cap);
+  for (int64_t i = 0; i < n; ++i) {
+    const int c = (int)(rng() % 10);
+    double x;
+    if (c < 4) x = -745.2 + U(rng) * (709.8 + 745.2);
+    else if (c < 6) x = 2.0 * U(rng) - 1.0;
+    else if (c < 7) x = (rng() & 1 ? -1.0 : 1.0) * bits(0x3c0, 0x3fe);
+    else if (c < 9) x = (rng() & 1 ? -1.0 : 1.0) * bits(0x3c4, 0x40a);
+    else x = (rng() & 1) ? 700.0 + 10.0 * U(rng) : -760.0 + 60.0 * U(rng);
+    a.exp_x.push_back(x);
+  }
+  for (int64_t i = 0; i < n; ++i) {
+    const int c = (int)(rng() % 10);
+    double x;
+    if (c < 3) x = bits(0, 0x7fe);
+    else if (c < 6) x = 1.0 + (U(rng) - 0.5) * 0.15;
+    else if (c < 8) x = 100.0 * U(rng);
+    else x = bits(1023 - 20, 1023 + 20);
+    if (!(x > 0.0)) x = 0.5;
+    a.log_x.push_back(x);
+  }
+  for (int64_t i = 0; i < n; ++i) {
+    const int cx = (int)(rng() % 10), cy = (int)(rng() % 10);
+    double x;
+    if (cx < 4) x = 1.0 + (U(rng) - 0.5);
+    else if (cx < 7) x = bits(0, 0x7fe);
+    else x = 1e4 * U(rng);
+    if (!(x > 0.0) || x == 1.0) x = 0.75;
+    double y;
+    if (cy < 3) y = 40.0 * U(rng) - 20.0;
+    else if (cy < 5) y = (double)((int64_t)(rng() % 81) - 40) * 0.5;
+    else if (cy < 7) y = 2000.0 * U(rng) - 1000.0;
+    else if (cy < 8) y = (rng() & 1 ? -1.0 : 1.0) * ((rng() & 1) ? bits(0x3b8, 0x3c4) : bits(0x43a, 0x444));
+    else {
+      const double lx = ::log(x);
+      y = lx != 0.0 ? (-760.0 + U(rng) * 1475.0) / lx : 3.0;
+    }
+    if (y == 0.0 || !std::isfinite(y)) y = 2.5;
+    a.pow_x.push_back(x);
+    a.pow_y.push_back(y);
+  }
+  return a;
+}
+
+py::tuple glibc_math_selfcheck_args(int64_t n, uint64_t seed) {
+  const GmArgs a = glibc_math_args(n, seed);
+  auto arr = [](const std::vector<double>& v) {
+    py::array_t<double> out((py::ssize_t)v.size());
+    if (!v.empty()) std::memcpy(out.mutable_data(), v.data(), v.size() * 8);
+    return out;
+  };
+  return py::make_tuple(arr(a.exp_x), arr(a.log_x), arr(a.pow_x), arr(a.pow_y));
+}
+
+py::dict glibc_math_selfcheck(int64_t n, uint64_t seed) {
   auto same = [](double a, double b) { return fksd::gm::asu(a) == fksd::gm::asu(b); };
   int64_t bad_exp = 0, bad_log = 0, bad_pow = 0;
   std::vector<std::pair<double, double>> e1, e2, e3;
   {
     py::gil_scoped_release rel;
-    for (int64_t i = 0; i < n; ++i) {
-      const int c = (int)(rng() % 10);
-      double x;
-      if (c < 4) x = -745.2 + U(rng) * (709.8 + 745.2);
-      else if (c < 6) x = 2.0 * U(rng) - 1.0;
-      else if (c < 7) x = (rng() & 1 ? -1.0 : 1.0) * bits(0x3c0, 0x3fe);
-      else if (c < 9) x = (rng() & 1 ? -1.0 : 1.0) * bits(0x3c4, 0x40a);
-      else x = (rng() & 1) ? 700.0 + 10.0 * U(rng) : -760.0 + 60.0 * U(rng);
+    const GmArgs a = glibc_math_args(n, seed);
+    for (const double x : a.exp_x) {
       double o = 0.0;
       const int st = fksd::gm::exp(x, o);
       const double g = ::exp(x);
       if (!same(o, g) || (st == 1) != std::isinf(g)) { if (bad_exp++ < 8) e1.push_back({x, 0.0}); }
     }
-    for (int64_t i = 0; i < n; ++i) {
-      const int c = (int)(rng() % 10);
-      double x;
-      if (c < 3) x = bits(0, 0x7fe);
-      else if (c < 6) x = 1.0 + (U(rng) - 0.5) * 0.15;
-      else if (c < 8) x = 100.0 * U(rng);
-      else x = bits(1023 - 20, 1023 + 20);
-      if (!(x > 0.0)) x = 0.5;
+    for (const double x : a.log_x) {
       double o = 0.0;
       fksd::gm::log(x, o);
       if (!same(o, ::log(x))) { if (bad_log++ < 8) e2.push_back({x, 0.0}); }
     }
-    for (int64_t i = 0; i < n; ++i) {
-      const int cx = (int)(rng() % 10), cy = (int)(rng() % 10);
-      double x;
-      if (cx < 4) x = 1.0 + (U(rng) - 0.5);
-      else if (cx < 7) x = bits(0, 0x7fe);
-      else x = 1e4 * U(rng);
-      if (!(x > 0.0) || x == 1.0) x = 0.75;
-      double y;
-      if (cy < 3) y = 40.0 * U(rng) - 20.0;
-      else if (cy < 5) y = (double)((int64_t)(rng() % 81) - 40) * 0.5;
-      else if (cy < 7) y = 2000.0 * U(rng) - 1000.0;
-      else if (cy < 8) y = (rng() & 1 ? -1.0 : 1.0) * ((rng() & 1) ? bits(0x3b8, 0x3c4) : bits(0x43a, 0x444));
-      else {
-        const double lx = ::log(x);
-        y = lx != 0.0 ? (-760.0 + U(rng) * 1475.0) / lx : 3.0;
-      }
-      if (y == 0.0 || !std::isfinite(y)) y = 2.5;
+    for (size_t i = 0; i < a.pow_x.size(); ++i) {
+      const double x = a.pow_x[i], y = a.pow_y[i];
       double o = 0.0;
       const int st = fksd::gm::pow(x, y, o);
       const double g = ::pow(x, y);
@@ -536,6 +790,13 @@ PYBIND11_MODULE(_fks_hip, m) {
   m.def("device_count", &device_count);
   m.def("test_wave_ops", &test_wave_ops);
   m.def("test_heap", &test_heap);
+  m.def("test_lane_acc", &test_lane_acc, py::arg("vals"), py::arg("offs"));
+  m.def("test_row_acc", &test_row_acc, py::arg("ops"), py::arg("vals"), py::arg("offs"), py::arg("inject"),
+        py::arg("meta"));
+  m.attr("TEST_ROW_OPS") = py::make_tuple("add", "add_unit", "stash_unit", "add_stash", "stash_drop");
+  m.def("test_fixed_div", &test_fixed_div, py::arg("lo"), py::arg("hi"), py::arg("n"));
+  m.def("test_div_by_recip", &test_div_by_recip, py::arg("d"), py::arg("hi"), py::arg("start") = 0,
+        py::arg("count") = -1);
   m.def("screen_linear", &screen_linear, py::arg("X"), py::arg("W"), py::arg("S"), py::arg("P"),
         py::arg("want_dec") = false, py::arg("device") = 0, py::arg("chunks") = 1);
   py::class_<DeviceEngine>(m, "DeviceEngine")
@@ -611,6 +872,7 @@ PYBIND11_MODULE(_fks_hip, m) {
     return py::make_tuple(st, out);
   });
   m.def("glibc_math_selfcheck", &glibc_math_selfcheck, py::arg("n"), py::arg("seed") = 1);
+  m.def("glibc_math_selfcheck_args", &glibc_math_selfcheck_args, py::arg("n"), py::arg("seed") = 1);
   m.def("gm_device_batch", &gm_device_batch, py::arg("fn"), py::arg("x"), py::arg("y"), py::arg("device") = 0);
 
 }

@@ -9,8 +9,9 @@
 // multiple of 2^-96 (or would overflow the 31 integer bits) sets `inexact`,
 // and callers recompute that policy with an arbitrary-precision path.
 //
-// Plain C++17 (host).  The HIP replay kernel carries its own device copy of
-// the same arithmetic (csrc/hip/exact_mean_dev.hip.h).
+// Plain C++17 (host).  The HIP replay kernels carry their own device copies of
+// the same arithmetic: LaneAcc and fixed_div_round_dev in
+// csrc/hip/device_common.h, RowAcc in csrc/hip/replay_rows.hip.h.
 #pragma once
 
 #include <cmath>
