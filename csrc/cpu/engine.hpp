@@ -218,6 +218,7 @@ SimResult simulate(const Workload& w, Scorer& scorer, const SimOptions& opt) {
   std::vector<int32_t> gpu_off(P + 1, 0);
   for (int p = 0; p < P; ++p) gpu_off[p + 1] = gpu_off[p] + std::max(0, w.pngpu[p]);
   std::vector<int32_t> assigned_gpus(gpu_off[P], -1);
+  std::vector<int64_t> start(opt.record_placements ? P : 0, -1);   // time of the creation event that placed the pod
   std::vector<uint8_t> waiting(P, 0);
   std::map<int32_t, int32_t> waiting_gmilli;  // multiset of gpu_milli of waiting GPU pods
   int64_t waiting_count = 0;
@@ -336,6 +337,7 @@ SimResult simulate(const Workload& w, Scorer& scorer, const SimOptions& opt) {
           }
         }
         assigned[p] = n;
+        if (opt.record_placements) start[p] = ev.time;
         if (waiting[p]) {
           waiting[p] = 0; --waiting_count;
           if (w.pngpu[p] > 0) {
@@ -399,7 +401,14 @@ SimResult simulate(const Workload& w, Scorer& scorer, const SimOptions& opt) {
     double s = overall - pen;
     res.score = std::max(0.0, std::min(1.0, s));
   }
-  if (opt.record_placements) res.placement = assigned;
+  if (opt.record_placements) {
+    res.placement = assigned;
+    res.placement_start = start;
+    res.placement_gpus.assign(P, 0);
+    for (int p = 0; p < P; ++p)
+      if (assigned[p] >= 0)
+        for (int k = gpu_off[p]; k < gpu_off[p + 1]; ++k) res.placement_gpus[p] |= (uint8_t)(1u << assigned_gpus[k]);
+  }
   return res;
 }
 

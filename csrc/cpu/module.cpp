@@ -18,6 +18,13 @@
 namespace py = pybind11;
 using namespace fks;
 
+template <class T>
+py::array_t<T> np_of(const std::vector<T>& v) {
+  py::array_t<T> a((py::ssize_t)v.size());
+  if (!v.empty()) std::memcpy(a.mutable_data(), v.data(), v.size() * sizeof(T));
+  return a;
+}
+
 namespace {
 
 template <class T>
@@ -77,7 +84,11 @@ py::dict to_dict(const SimResult& r) {
   d["n_dropped"] = r.n_dropped; d["inexact"] = r.inexact; d["trace_hash"] = r.trace_hash;
   if (!r.snap_values.empty()) d["snap_values"] = r.snap_values;
   if (!r.frag_values.empty()) d["frag_values"] = r.frag_values;
-  if (!r.placement.empty()) d["placement"] = r.placement;
+  if (!r.placement.empty()) {
+    d["placement"] = r.placement;
+    d["placement_gpus"] = np_of(r.placement_gpus);
+    d["placement_start"] = np_of(r.placement_start);
+  }
   if (!r.states.empty()) {
     py::array_t<int32_t> a((py::ssize_t)r.states.size());
     std::memcpy(a.mutable_data(), r.states.data(), r.states.size() * 4);
@@ -127,14 +138,36 @@ struct NativeHostScorer {
   }
 };
 
-}  // namespace
+// The schedules of a batch (record_placements): per policy the node, GPU mask
+// and start time of every pod in trace order, beside the result table.  A
+// replay that raises returns no schedule: its arrays stay at -1 / 0 / -1.
+struct ScheduleOut {
+  py::array_t<double> rows;
+  py::array_t<int32_t> node;
+  py::array_t<uint8_t> gpus;
+  py::array_t<int64_t> start;
+  ScheduleOut(int64_t P, int64_t n)
+      : rows({P, (int64_t)kCols}), node({P, n}), gpus({P, n}), start({P, n}) {
+    std::fill_n(node.mutable_data(), P * n, -1);
+    std::fill_n(gpus.mutable_data(), P * n, (uint8_t)0);
+    std::fill_n(start.mutable_data(), P * n, (int64_t)-1);
+  }
+  // (called off the GIL: raw pointers only)
+  struct Raw {
+    double* rows; int32_t* node; uint8_t* gpus; int64_t* start; int64_t n;
+    void put(int64_t i, const SimResult& r) const {
+      fill_row(rows + i * kCols, r);
+      if (r.exc != EXC_NONE || (int64_t)r.placement.size() != n) return;
+      std::copy(r.placement.begin(), r.placement.end(), node + i * n);
+      std::copy(r.placement_gpus.begin(), r.placement_gpus.end(), gpus + i * n);
+      std::copy(r.placement_start.begin(), r.placement_start.end(), start + i * n);
+    }
+  };
+  Raw raw() { return Raw{rows.mutable_data(), node.mutable_data(), gpus.mutable_data(), start.mutable_data(), node.shape(1)}; }
+  py::tuple tuple() const { return py::make_tuple(rows, node, gpus, start); }
+};
 
-template <class T>
-py::array_t<T> np_of(const std::vector<T>& v) {
-  py::array_t<T> a((py::ssize_t)v.size());
-  if (!v.empty()) std::memcpy(a.mutable_data(), v.data(), v.size() * sizeof(T));
-  return a;
-}
+}  // namespace
 
 namespace fks {
 
@@ -273,6 +306,54 @@ PYBIND11_MODULE(_fks_cpu, m) {
       });
     }
     return out;
+  }, py::arg("workload"), py::arg("codes"), py::arg("fconsts"), py::arg("iconsts"), py::arg("ctags"),
+     py::arg("options") = py::dict(), py::arg("threads") = 1);
+
+  // Schedules of a batch, threaded like the batch calls above: (rows [P, 13],
+  // node [P, n_pods] int32, GPU mask [P, n_pods] uint8, start [P, n_pods] int64).
+  m.def("schedule_builtin_batch", [](const Workload& w, py::array_t<int32_t, py::array::c_style | py::array::forcecast> fam,
+                                     py::array_t<double, py::array::c_style | py::array::forcecast> weights,
+                                     py::dict opts, int threads) {
+    const int64_t P = fam.size(), K = weights.ndim() > 1 ? weights.shape(1) : 0;
+    if (weights.ndim() != 2 || weights.shape(0) != P) throw std::invalid_argument("weights must be [P, K] float64");
+    SimOptions o = make_options(opts);
+    o.record_placements = true;
+    ScheduleOut out(P, w.n_pods);
+    const ScheduleOut::Raw raw = out.raw();
+    const int32_t* fp = fam.data();
+    const double* wp = weights.data();
+    {
+      py::gil_scoped_release rel;
+      parallel_for(P, threads, [&](int64_t i) {
+        BuiltinScorer sc; sc.family = fp[i];
+        for (int64_t k = 0; k < K && k < 16; ++k) sc.w[k] = wp[i * K + k];
+        raw.put(i, simulate(w, sc, o));
+      });
+    }
+    return out.tuple();
+  }, py::arg("workload"), py::arg("families"), py::arg("weights"), py::arg("options") = py::dict(), py::arg("threads") = 1);
+
+  m.def("schedule_program_batch", [](const Workload& w, std::vector<py::bytes> codes,
+                                     std::vector<std::vector<double>> fconsts,
+                                     std::vector<std::vector<int64_t>> iconsts,
+                                     std::vector<std::vector<uint8_t>> ctags, py::dict opts, int threads) {
+    const int64_t P = (int64_t)codes.size();
+    std::vector<Program> progs;
+    for (int64_t i = 0; i < P; ++i) progs.push_back(make_program(std::string(codes[i]), fconsts[i], iconsts[i], ctags[i]));
+    SimOptions o = make_options(opts);
+    o.record_placements = true;
+    ScheduleOut out(P, w.n_pods);
+    const ScheduleOut::Raw raw = out.raw();
+    {
+      py::gil_scoped_release rel;
+      parallel_for(P, threads, [&](int64_t i) {
+        VmScorer sc(progs[i], o.budget);
+        SimResult r = simulate(w, sc, o);
+        if (r.exc == EXC_NONE && sc.exc) r.exc = sc.exc;
+        raw.put(i, r);
+      });
+    }
+    return out.tuple();
   }, py::arg("workload"), py::arg("codes"), py::arg("fconsts"), py::arg("iconsts"), py::arg("ctags"),
      py::arg("options") = py::dict(), py::arg("threads") = 1);
 

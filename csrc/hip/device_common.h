@@ -46,6 +46,32 @@ __device__ __forceinline__ const FKS_CONST T* const_ptr(const T* p) { return (co
 
 __device__ __forceinline__ int lane_id() { return __lane_id(); }
 
+// Schedule mode (separate kernel instances, launch.h): what a replay did, one
+// record per (policy, pod rank) -- the time of the creation event that placed
+// the pod, its node and its GPUs on that node (bit j = GPU j).  The host fills
+// the buffer with 0xFF bytes ahead of the launch (never placed: start and node
+// -1); a pod is committed at most once per replay, so each record is written
+// at most once, by one lane, with one plain 16-byte store.
+struct SchedRec {
+  int64_t start;
+  int32_t node;
+  int32_t gpu_mask;
+};
+static_assert(sizeof(SchedRec) == 16, "one 16-byte store per record");
+__device__ __forceinline__ void sched_put(SchedRec* rec, int64_t t, int node, int gmask) {
+  typedef int sched_v4i __attribute__((ext_vector_type(4)));
+  const sched_v4i v = {(int)(uint32_t)(uint64_t)t, (int)(uint32_t)((uint64_t)t >> 32), node, gmask};
+  *reinterpret_cast<FKS_GLOBAL sched_v4i*>(global_ptr(rec)) = v;
+}
+// The schedule sink of the one-wave replay (replay.hip.h): NoSched compiles to nothing.
+struct NoSched {
+  static constexpr bool kOn = false;
+};
+struct SchedSink {
+  static constexpr bool kOn = true;
+  SchedRec* rec;   // the policy's n_pods records
+};
+
 __device__ __forceinline__ int uni(int x) { return __builtin_amdgcn_readfirstlane(x); }
 __device__ __forceinline__ uint32_t uni(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
 __device__ __forceinline__ int64_t uni64(int64_t x) {

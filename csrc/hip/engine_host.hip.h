@@ -184,6 +184,8 @@ struct Slot {
   hipStream_t stream = nullptr;
   hipEvent_t done = nullptr;
   DevBuf res, tab, fam, w, code, meta, kpay, ktag, gheap, prof, queue, kc;
+  DevBuf sched;         // schedule launches: [P, n_pods] SchedRec, reserved on first use
+  int sched_P = 0;      // policies of the schedule batch in flight (0: an ordinary batch)
   HostBuf h_in, h_tab;
   bool fused_table = false;   // the launch wrote h_tab itself (row kernels)
   int P = 0;
@@ -192,7 +194,7 @@ struct Slot {
   bool busy = false;
   roctx_range_id_t range = 0;   // roctx range spanning submit -> wait (rocprofv3 --marker-trace)
   void release() {
-    for (DevBuf* b : {&res, &tab, &fam, &w, &code, &meta, &kpay, &ktag, &gheap, &prof, &queue, &kc}) b->release();
+    for (DevBuf* b : {&res, &tab, &fam, &w, &code, &meta, &kpay, &ktag, &gheap, &prof, &queue, &kc, &sched}) b->release();
     h_in.release();
     h_tab.release();
     if (done) (void)hipEventDestroy(done);
@@ -335,6 +337,12 @@ class DeviceEngine {
       max_events_ = (uint32_t)me;
     }
     if (o.contains("heap_top")) heap_top_opt_ = o["heap_top"].cast<int>();   // -1: auto
+    // schedule launches: most bytes of records one slot holds (larger batches run in chunks)
+    if (o.contains("schedule_bytes")) {
+      const int64_t b = o["schedule_bytes"].cast<int64_t>();
+      if (b < 1) throw std::invalid_argument("schedule_bytes must be positive");
+      sched_cap_ = (size_t)b;
+    }
     if (o.contains("partial_delmap")) partial_delmap_off_ = !o["partial_delmap"].cast<bool>();   // A/B
     if (o.contains("trace_hash")) W_.trace_hash = o["trace_hash"].cast<bool>() ? 1 : 0;
     if (o.contains("check_invariants")) {
@@ -454,9 +462,93 @@ class DeviceEngine {
     return py::make_tuple(tab, prof);
   }
 
+  // ---- schedule mode: what each replay did, beside its row ---------------------------------
+  // A schedule batch runs on the schedule instances (launch.h): mixed family /
+  // HBM heap / two-wave native, whatever the batch and `heap_mode` would pick
+  // otherwise; the other options hold.  wait_schedule(slot) returns the rows and
+  // the records [P, n_pods, 4] int32 (start lo, start hi, node, GPU mask) by pod
+  // rank.  At most schedule_chunk() policies per batch (the `schedule_bytes` cap).
+  int schedule_chunk() const {
+    const size_t per = (size_t)W_.n_pods * sizeof(SchedRec);
+    return (int)std::max<size_t>(1, std::min<size_t>(sched_cap_ / per, (size_t)INT32_MAX));
+  }
+  void schedule_guard(int P) const {
+    if (P < 1) throw std::invalid_argument("empty batch");
+    if (W_.check_every > 0)
+      throw std::invalid_argument("schedule mode and check_invariants cannot be combined: the schedule instances "
+                                  "carry no invariant check (set check_invariants to 0)");
+    if (P > schedule_chunk())
+      throw std::invalid_argument("schedule batch exceeds the schedule_bytes cap: at most schedule_chunk() policies");
+  }
+  // the slot's record buffer, filled with "never placed" on the launch's own stream
+  SchedRec* schedule_begin(Slot& s, int P) {
+    const size_t bytes = (size_t)P * (size_t)W_.n_pods * sizeof(SchedRec);
+    s.sched.reserve(bytes);
+    HIP_OK(hipMemsetAsync(s.sched.p, 0xFF, bytes, s.stream));
+    return s.sched.as<SchedRec>();
+  }
+
+  void submit_builtin_schedule(int slot, py::array_t<int32_t, py::array::c_style | py::array::forcecast> fam,
+                               py::array_t<double, py::array::c_style | py::array::forcecast> weights) {
+    Slot& s = idle_slot(slot);
+    const int P = (int)fam.size();
+    if (weights.ndim() != 2 || weights.shape(0) != P || weights.shape(1) != kWeights)
+      throw std::invalid_argument("weights must be [P, 16] float64");
+    schedule_guard(P);
+    HIP_OK(hipSetDevice(device_));
+    s.range = roctxRangeStartA("fks.batch.builtin.schedule");
+    stage_builtin(s, fam.data(), weights.data(), P);
+    s.fam_spec = -1;   // the mixed-family instance
+    {
+      py::gil_scoped_release rel;
+      SchedRec* rec = schedule_begin(s, P);
+      if (use_rows()) {
+        launch_rows(s, false, rec);
+      } else {
+        const DevWorkload Wl = launch_workload(true, 0, false);
+        const size_t lds = lds_bytes(true, Wl.heap_top, 0);
+        if (lds > kMaxLds) throw std::invalid_argument("replay layout exceeds the 160 KiB LDS");
+        const size_t wb = (size_t)P * kWeights * 8;
+        const fksk::BuiltinArgs a{Wl, nullptr, reinterpret_cast<const int32_t*>(s.h_in.dev<char>() + wb),
+                                  s.h_in.dev<double>(), s.w.as<double>(), s.res.as<DevResult>(), gheap_for(s, P), nullptr};
+        HIP_OK(fksk::launch_builtin_sched(npass_, P, lds, s.stream, a, rec));
+      }
+      finish(s);
+    }
+    s.sched_P = P;
+  }
+
+  void submit_native_schedule(int slot, py::array_t<uint64_t, py::array::c_style | py::array::forcecast> fn,
+                              py::array_t<int64_t, py::array::c_style | py::array::forcecast> kc,
+                              py::array_t<int32_t, py::array::c_style | py::array::forcecast> koff) {
+    schedule_guard((int)fn.size());
+    submit_native_impl(slot, fn, kc, koff, false, true);
+    slot_at(slot).sched_P = (int)fn.size();
+  }
+
+  py::tuple wait_schedule(int slot) {
+    Slot& s = slot_at(slot);
+    if (!s.busy || s.sched_P != s.P || s.P < 1) throw std::invalid_argument("slot has no schedule batch in flight");
+    const int P = s.P;
+    py::array_t<double> rows = wait(slot);
+    py::array_t<int32_t> rec({(py::ssize_t)P, (py::ssize_t)W_.n_pods, (py::ssize_t)4});
+    int32_t* dst = rec.mutable_data();
+    {
+      // after the slot's event: the records come back on its stream
+      py::gil_scoped_release rel;
+      HIP_OK(hipSetDevice(device_));
+      HIP_OK(hipMemcpyAsync(dst, s.sched.p, (size_t)P * (size_t)W_.n_pods * sizeof(SchedRec), hipMemcpyDeviceToHost,
+                            s.stream));
+      HIP_OK(hipStreamSynchronize(s.stream));
+    }
+    s.sched_P = 0;
+    return py::make_tuple(rows, rec);
+  }
+
   void submit_native_impl(int slot, py::array_t<uint64_t, py::array::c_style | py::array::forcecast> fn,
                           py::array_t<int64_t, py::array::c_style | py::array::forcecast> kc,
-                          py::array_t<int32_t, py::array::c_style | py::array::forcecast> koff, bool profiled) {
+                          py::array_t<int32_t, py::array::c_style | py::array::forcecast> koff, bool profiled,
+                          bool schedule = false) {
     Slot& s = idle_slot(slot);
     const int P = (int)fn.size();
     if (P < 1) throw std::invalid_argument("empty batch");
@@ -484,12 +576,13 @@ class DeviceEngine {
     const int64_t* kc_dev = reinterpret_cast<const int64_t*>(s.h_in.dev<char>() + kco);
     {
       py::gil_scoped_release rel;
+      SchedRec* rec = schedule ? schedule_begin(s, P) : nullptr;
       if (use_rows()) {
-        launch_rows_native(s, P, fb, kc_dev, profiled);
+        launch_rows_native(s, P, fb, kc_dev, profiled, rec);
         finish(s);
         return;
       }
-      const bool g = use_gheap_native(P);
+      const bool g = schedule || use_gheap_native(P);   // (the schedule instance: HBM heap)
       // kKcLds / 64 VM-register rows of LDS hold the policy's constant block
       const DevWorkload Wl = launch_workload(g, kKcLds / kWave, false);
       const size_t lds = lds_bytes(g, Wl.heap_top, kKcLds / kWave);
@@ -497,7 +590,8 @@ class DeviceEngine {
       uint64_t* gh = g ? gheap_for(s, P) : nullptr;
       const fksk::NativeArgs a{Wl, nullptr, s.h_in.dev<const uint64_t>(), kc_dev,
                                reinterpret_cast<const int32_t*>(s.h_in.dev<char>() + fb), s.res.as<DevResult>(), gh};
-      HIP_OK(fksk::launch_native(npass_, g, P, lds, s.stream, a));
+      HIP_OK(rec ? fksk::launch_native_sched(npass_, P, lds, s.stream, a, rec)
+                 : fksk::launch_native(npass_, g, P, lds, s.stream, a));
       finish(s);
     }
   }
@@ -1125,6 +1219,7 @@ class DeviceEngine {
     s.h_tab.reserve(sizeof(double) * 13 * (size_t)P);
     s.w.reserve(sizeof(double) * kWeights * (size_t)P);
     s.P = P;
+    s.sched_P = 0;
   }
 
   // numpy -> pinned staging -> device (async on the slot's stream)
@@ -1203,14 +1298,17 @@ class DeviceEngine {
   }
 
   // row kernel launch (optionally the phase-profiled build); returns the wave count
-  int launch_rows(Slot& s, bool profiled) {
+  // rec: the schedule instance (mixed family) and its record buffer
+  int launch_rows(Slot& s, bool profiled, SchedRec* rec = nullptr) {
     const int P = s.P;
     DevWorkload Wl = W_;
     const int kf = s.fam_spec != FAM_COMPOSITE_LINEAR ? s.fam_spec
                    : comp_waves_ == 5                  ? kRowCompositeW5
                    : !row_flat_                        ? kRowCompositeSplit
                                                        : s.fam_spec;
-    const std::pair<int, int> lay = row_layout(kf);
+    std::pair<int, int> lay = row_layout(kf);
+    if (rec)   // the layout of the mixed instance; residency as the schedule instance's registers allow
+      lay.second = std::max(1, std::min(lay.second, fksk::rows_sched_waves_per_cu(rows_lds_bytes(W_.n_pods, lay.first))));
     Wl.heap_top = lay.first;
     const size_t lds = std::max(rows_lds_bytes(W_.n_pods, Wl.heap_top) + (profiled ? kRowProfBytes : 0), row_min_lds_);
     if (lds > kMaxLds) throw std::invalid_argument("row kernel layout exceeds the 160 KiB LDS");
@@ -1228,7 +1326,8 @@ class DeviceEngine {
                               s.h_in.dev<double>(), s.w.as<double>(), s.res.as<DevResult>(), s.gheap.as<uint64_t>(),
                               profiled ? s.prof.as<uint64_t>() : nullptr, s.h_tab.dev<double>()};
     s.fused_table = true;
-    if (profiled) HIP_OK(fksk::launch_builtin_rows_prof(kf, P, waves, s.queue.as<uint32_t>(), s.qbase, lds, s.stream, a));
+    if (rec) HIP_OK(fksk::launch_builtin_rows_sched(P, waves, s.queue.as<uint32_t>(), s.qbase, lds, s.stream, a, rec));
+    else if (profiled) HIP_OK(fksk::launch_builtin_rows_prof(kf, P, waves, s.queue.as<uint32_t>(), s.qbase, lds, s.stream, a));
     else HIP_OK(fksk::launch_builtin_rows(kf, P, waves, s.queue.as<uint32_t>(), s.qbase, lds, s.stream, a));
     s.qbase += (uint32_t)P + (uint32_t)waves * kRowsPerWave;   // every row makes one final, empty claim
     return waves;
@@ -1262,13 +1361,15 @@ class DeviceEngine {
     return T;
   }
 
-  void launch_rows_native(Slot& s, int P, size_t fn_bytes, const int64_t* kc_dev, bool profiled = false) {
+  void launch_rows_native(Slot& s, int P, size_t fn_bytes, const int64_t* kc_dev, bool profiled = false,
+                          SchedRec* rec = nullptr) {
     // the two-wave kernel for every batch (its heap top follows the programs in
     // flight); four programs per wave only on request (native_rows = 4)
-    const int ra = native_rows_opt_ > 0 ? native_rows_opt_ : (native_duo_ || P <= 2 * num_cus_ ? 1 : kRowsPerWave);
+    // (rec: a schedule launch runs the two-wave schedule instance, whatever `native_duo` / `native_rows` say)
+    const int ra = rec ? 1 : native_rows_opt_ > 0 ? native_rows_opt_ : (native_duo_ || P <= 2 * num_cus_ ? 1 : kRowsPerWave);
     DevWorkload Wl = W_;
     const int entries = row_heap_entries(W_.n_pods);
-    if (ra == 1 && native_duo_) {
+    if (ra == 1 && (native_duo_ || rec)) {
       // two waves per program (heap wave + scoring wave, replay_duo.hip.h)
       const int T = duo_top(std::max(P, native_inflight_));
       Wl.heap_top = T;
@@ -1287,7 +1388,8 @@ class DeviceEngine {
       if (std::getenv("FKS_DEBUG_LAUNCH"))
         std::fprintf(stderr, "[fks] native duo: P=%d T=%d lds=%zu per_cu=%d stream=%p\n", P, T, lds,
                      last_duo_per_cu_, (void*)s.stream);
-      HIP_OK(fksk::launch_native_duo(P, lds, s.stream, a, nat));
+      HIP_OK(rec ? fksk::launch_native_duo_sched(P, lds, s.stream, a, nat, rec)
+                 : fksk::launch_native_duo(P, lds, s.stream, a, nat));
       last_native_rows_ = 0;   // 0: the two-wave kernel
       last_native_waves_ = 2 * P;
       return;
@@ -1385,6 +1487,7 @@ class DeviceEngine {
   std::string heap_mode_ = "auto";
   int64_t budget_ = 0;
   uint32_t max_events_ = 0;
+  size_t sched_cap_ = size_t(256) << 20;   // `schedule_bytes`: record bytes per slot
   int heap_top_opt_ = -1;
   bool partial_delmap_off_ = false;
   bool wave_duo_ = false;   // NPASS-4 builtin launches on the two-wave kernel (`wave_duo`)

@@ -170,6 +170,21 @@ static_assert(offsetof(ServiceArgs, a) == 0, "BuiltinArgs (and its DevWorkload) 
 hipError_t launch_native_service(int blocks, size_t lds, hipStream_t stream, const ServiceArgs& s);
 int native_service_blocks_per_cu(size_t lds);
 
+// Schedule mode: separate instances that also store one fksd::SchedRec per
+// placed pod into rec[p * n_pods + rank] (device_common.h; the host fills the
+// buffer with 0xFF bytes first).  One row each in a table of its own: the
+// mixed-family HBM-heap one-wave kernel per NPASS, the mixed-family row kernel,
+// the HBM-heap one-wave native kernel per NPASS and the two-wave native kernel.
+// rec is a trailing kernel parameter, so no argument of the other instances moves.
+hipError_t launch_builtin_sched(int npass, int P, size_t lds, hipStream_t s, const BuiltinArgs& a, fksd::SchedRec* rec);
+hipError_t launch_builtin_rows_sched(int P, int waves, uint32_t* queue, uint32_t qbase, size_t lds, hipStream_t s,
+                                     const BuiltinArgs& a, fksd::SchedRec* rec);
+int rows_sched_waves_per_cu(size_t lds);
+hipError_t launch_native_sched(int npass, int P, size_t lds, hipStream_t s, const NativeArgs& a, fksd::SchedRec* rec);
+hipError_t launch_native_duo_sched(int P, size_t lds, hipStream_t stream, const BuiltinArgs& a,
+                                   const fksd::RowNativeArgs& nat, fksd::SchedRec* rec);
+int native_duo_sched_blocks_per_cu(size_t lds);
+
 // addresses of the native programs' runtime library (fks_rt_binop, fks_rt_unop, register floor)
 hipError_t native_rt_table(uint64_t* dev_out, hipStream_t s);
 // glibc_math.h on the device (tests): fn 0 exp, 1 log, 2 pow; n arguments, one per lane

@@ -827,6 +827,10 @@ PYBIND11_MODULE(_fks_hip, m) {
       .def("submit_native", &DeviceEngine::submit_native)
       .def("evaluate_native", &DeviceEngine::evaluate_native)
       .def("profile_native", &DeviceEngine::profile_native)
+      .def("submit_builtin_schedule", &DeviceEngine::submit_builtin_schedule)
+      .def("submit_native_schedule", &DeviceEngine::submit_native_schedule)
+      .def("wait_schedule", &DeviceEngine::wait_schedule)
+      .def("schedule_chunk", &DeviceEngine::schedule_chunk)
       .def("native_rt_table", &DeviceEngine::native_rt_table);
   py::class_<DeviceSuite>(m, "DeviceSuite")
       .def(py::init<py::list, int>(), py::arg("engines"), py::arg("n_slots") = 4)

@@ -579,11 +579,13 @@ struct WaveNodes {
 // decode, delete, the repush time and snapshot are calls of the steps above;
 // place, fail and pick / commit are this kernel's own copies of WaveNodes'
 // (comments at each say why), held to them by the device tests alone.
-template <int NPASS, class Scorer, class Prof = NoProf, bool FLAT = false>
+// Sched = SchedSink (schedule-mode instances): every commit also stores the
+// pod's record (device_common.h SchedRec); NoSched adds nothing.
+template <int NPASS, class Scorer, class Prof = NoProf, bool FLAT = false, class Sched = NoSched>
 __device__ void replay_one(const DevWorkload& W, const DevWorkload* Wcold, Scorer& scorer, FKS_GLOBAL uint64_t* hbuf,
                            FKS_LDS uint64_t* htop, int T, FKS_LDS uint32_t* delmap, FKS_LDS int32_t* inv,
                            DevResult* out,
-                           uint64_t* prof_out = nullptr) {
+                           uint64_t* prof_out = nullptr, Sched sched = Sched{}) {
   // W: the kernel-argument copy (hot fields, kept in SGPRs); Wcold: the same
   // struct in global memory (cold_ptr).
   // hbuf: the policy's heap array -- LDS (fast, 2 policies/CU on the 8k trace)
@@ -782,6 +784,9 @@ __device__ void replay_one(const DevWorkload& W, const DevWorkload* Wcold, Score
                          ((uint64_t)best_node << 2) | kDelete);
         ++n;
         if (W.trace_hash) ns.hsh = mix_event(ns.hsh, ((uint64_t)(uint32_t)rank << 2), ((uint64_t)t << 8) ^ (uint64_t)best_node);
+        if constexpr (Sched::kOn) {
+          if (lane == 0) sched_put(sched.rec + rank, t, best_node, gmask);
+        }
         prof.mark(PH_COMMIT);
       }
     }

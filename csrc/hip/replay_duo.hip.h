@@ -226,10 +226,12 @@ __device__ void pop_reinsert64(const RowHeap& hp, int n, uint64_t last, int j, u
 // called the service's rate was 1.5 % lower in every run
 // (profiles/r8_twin_steps_ab.txt).  As written here the two compile to the
 // machine code they had before the functions existed.
-template <bool PROF = false>
+// SCHED (schedule-mode instance): the scoring wave also stores every placed
+// pod's record into sched[p * n_pods + rank] (device_common.h SchedRec).
+template <bool PROF = false, bool SCHED = false>
 __device__ void replay_duo(const DevWorkload& W, const DevWorkload* Wdev, uint64_t* gheap, DevResult* out,
                            RowNativeArgs nat, double* table, uint64_t* prof_out = nullptr, int slot = -1,
-                           int hslot = -1) {
+                           int hslot = -1, SchedRec* sched = nullptr) {
   uint64_t pacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   uint64_t plast = 0;
   auto mark = [&](int ph) {
@@ -622,6 +624,9 @@ __device__ void replay_duo(const DevWorkload& W, const DevWorkload* Wdev, uint64
         // answer first: H's push runs while S commits
         reply(DUO_PLACED, (dt << tshift) | ((uint64_t)rank << lb) | ((uint64_t)gmask << (2 + nb)) |
                               ((uint64_t)best_node << 2) | kDelete, k);
+        if constexpr (SCHED) {
+          if (jv == best_node) sched_put(sched + (size_t)p * N + rank, t, best_node, gmask);
+        }
         if (jv == best_node) {
           nr.cpu_left[0] -= pod.cpu;
           nr.mem_left[0] -= pod.mem;

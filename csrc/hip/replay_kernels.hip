@@ -185,6 +185,24 @@ constexpr std::array<Row<fksk::BuiltinArgs>, sizeof...(F)> builtin_rows(Keys<F..
 }
 #endif
 
+#if FKS_KIND == 0
+// Schedule mode: the mixed-family, HBM-heap instance that also stores every
+// commit's record (rec: [P, n_pods], a trailing parameter -- the arguments of
+// the instances above do not move).
+template <int NPASS>
+__global__ FKS_FAM_BOUNDS(true, -1, NPASS) void k_replay_builtin_sched(fksk::BuiltinArgs a, SchedRec* rec) {
+  const int p = blockIdx.x;
+  const Slot s = policy_slot<true>(a.W, a.gheap, p);
+  BuiltinScorerDev<-1> sc;
+  load_policy<-1>(sc, a, p);
+  replay_one<NPASS, BuiltinScorerDev<-1>, NoProf, FKS_WAVE_FLAT != 0, SchedSink>(
+      a.W, kernarg_workload(), sc, s.h, s.top, s.T, s.delmap, s.inv, a.out + p, nullptr,
+      SchedSink{rec + (size_t)p * a.W.n_pods});
+}
+constexpr std::array<Row<fksk::BuiltinArgs, SchedRec*>, 1> kBuiltinSched = {
+    {{0, k_replay_builtin_sched<FKS_NPASS>}}};
+#endif
+
 #if FKS_KIND == 0 && FKS_NPASS == 4
 // 256-node clusters, HBM heap: heap wave + scoring wave per policy
 // (replay_wave_duo.hip.h); both waves share the register allocation of the
@@ -296,6 +314,15 @@ void k_replay_rows_prof(fksk::BuiltinArgs a, int P, uint32_t* queue, uint32_t qb
   replay_rows<FAM, RowProf>(a.W, kernarg_workload(), a.fam, a.weights, a.gheap, a.out, P, queue, qbase, a.prof,
                             RowNativeArgs{nullptr, nullptr, nullptr}, kRowsPerWave, a.table);
 }
+// Schedule mode: the mixed-family instance that also stores every commit's record (rec: [P, n_pods])
+__global__ __launch_bounds__(64, 2) void k_replay_rows_sched(fksk::BuiltinArgs a, int P, uint32_t* queue, uint32_t qbase,
+                                                             SchedRec* rec) {
+  replay_rows<-1, RowNoProf, FKS_ROW_FLAT != 0, true>(a.W, kernarg_workload(), a.fam, a.weights, a.gheap, a.out, P, queue,
+                                                      qbase, nullptr, RowNativeArgs{nullptr, nullptr, nullptr},
+                                                      kRowsPerWave, a.table, rec);
+}
+constexpr std::array<Row<fksk::BuiltinArgs, int, uint32_t*, uint32_t, SchedRec*>, 1> kRowsSched = {
+    {{0, k_replay_rows_sched}}};
 using RowsRow = Row<fksk::BuiltinArgs, int, uint32_t*, uint32_t>;
 template <int... F>
 constexpr std::array<RowsRow, sizeof...(F) + 2> rows_rows(Keys<F...>) {
@@ -375,6 +402,10 @@ __global__ __launch_bounds__(128, 1) void k_replay_native_duo(fksk::BuiltinArgs 
 // s_memtime-profiled build (diagnostics): a.prof = [blocks, 2 waves, 8] cycles
 __global__ __launch_bounds__(128, 1) void k_replay_native_duo_prof(fksk::BuiltinArgs a, RowNativeArgs nat) {
   replay_duo<true>(a.W, kernarg_workload(), a.gheap, a.out, nat, a.table, a.prof);
+}
+// Schedule mode: the scoring wave also stores every placed pod's record (rec: [P, n_pods])
+__global__ __launch_bounds__(128, 1) void k_replay_native_duo_sched(fksk::BuiltinArgs a, RowNativeArgs nat, SchedRec* rec) {
+  replay_duo<false, true>(a.W, kernarg_workload(), a.gheap, a.out, nat, a.table, nullptr, -1, -1, rec);
 }
 // ----------------------------------------------------------------------------
 // The resident program service: a resident pool of two-wave workgroups that replays
@@ -566,6 +597,25 @@ __global__ __launch_bounds__(64, GHEAP ? 2 : 1) void k_replay_native(fksk::Nativ
   sc.kc = kl;
   replay_one<NPASS>(a.W, kernarg_workload(), sc, s.h, s.top, s.T, s.delmap, s.inv, a.out + p);
 }
+// Schedule mode: the HBM-heap instance that also stores every commit's record (rec: [P, n_pods])
+template <int NPASS>
+__global__ __launch_bounds__(64, 2) void k_replay_native_sched(fksk::NativeArgs a, SchedRec* rec) {
+  const int p = blockIdx.x;
+  const Slot s = policy_slot<true>(a.W, a.gheap, p);
+  NativeScorerDev sc;
+  sc.fn = prog_of(uniu64(a.fn[p]));
+  sc.feas = prog_feas(uniu64(a.fn[p]));
+  sc.gmem = a.W.gmem_total;
+  const FKS_GLOBAL int64_t* ksrc = global_ptr(a.kc + a.koff[p]);   // as k_replay_native
+  FKS_LDS int64_t* kl = reinterpret_cast<FKS_LDS int64_t*>(lds_ptr(s.vregs));
+  for (int i = lane_id(); i < kKcLds; i += kWave) kl[i] = ksrc[i];
+  sc.kc = kl;
+  replay_one<NPASS, NativeScorerDev, NoProf, false, SchedSink>(a.W, kernarg_workload(), sc, s.h, s.top, s.T, s.delmap,
+                                                                   s.inv, a.out + p, nullptr,
+                                                                   SchedSink{rec + (size_t)p * a.W.n_pods});
+}
+constexpr std::array<Row<fksk::NativeArgs, SchedRec*>, 1> kNativeSched = {
+    {{0, k_replay_native_sched<FKS_NPASS>}}};
 template <int... G>
 constexpr std::array<Row<fksk::NativeArgs>, sizeof...(G)> native_rows(Keys<G...>) {
   return {{{G, k_replay_native<FKS_NPASS, G != 0>}...}};
@@ -577,6 +627,8 @@ constexpr std::array<Row<fksk::BuiltinArgs, RowNativeArgs, int, uint32_t*, uint3
     {{0, k_replay_rows_native}, {1, k_replay_rows_native_prof}}};
 constexpr std::array<Row<fksk::BuiltinArgs, RowNativeArgs>, 2> kNativeDuo = {
     {{0, k_replay_native_duo}, {1, k_replay_native_duo_prof}}};
+constexpr std::array<Row<fksk::BuiltinArgs, RowNativeArgs, SchedRec*>, 1> kNativeDuoSched = {
+    {{0, k_replay_native_duo_sched}}};
 constexpr std::array<Row<fksk::ServiceArgs>, 1> kService = {{{0, k_native_service}}};
 constexpr std::array<Row<fksk::SuiteArgs, RowNativeArgs>, 1> kNativeDuoSuite = {{{0, k_replay_native_duo_suite}}};
 #endif
@@ -592,6 +644,8 @@ template <int KIND, int NPASS> hipError_t unit_attrs(int max_lds);
 template <int NPASS> hipError_t unit_launch_builtin(bool gheap, int fam, int P, size_t lds, hipStream_t s, const BuiltinArgs& a);
 template <int NPASS> hipError_t unit_launch_vm(bool gheap, int P, size_t lds, hipStream_t s, const VmArgs& a);
 template <int NPASS> hipError_t unit_launch_native(bool gheap, int P, size_t lds, hipStream_t s, const NativeArgs& a);
+template <int NPASS> hipError_t unit_launch_builtin_sched(int P, size_t lds, hipStream_t s, const BuiltinArgs& a, SchedRec* rec);
+template <int NPASS> hipError_t unit_launch_native_sched(int P, size_t lds, hipStream_t s, const NativeArgs& a, SchedRec* rec);
 
 #if FKS_KIND == 0
 template <>
@@ -604,8 +658,12 @@ hipError_t launch_builtin_wave_duo(int fam, int P, size_t lds, hipStream_t s, co
 }
 #endif
 template <>
+hipError_t unit_launch_builtin_sched<FKS_NPASS>(int P, size_t lds, hipStream_t s, const BuiltinArgs& a, SchedRec* rec) {
+  return launch_row(kBuiltinSched, 0, dim3(P), dim3(64), lds, s, a, rec);
+}
+template <>
 hipError_t unit_attrs<0, FKS_NPASS>(int mx) {
-  hipError_t e = raise_lds(mx, kBuiltinHbm, kBuiltinLds);
+  hipError_t e = raise_lds(mx, kBuiltinHbm, kBuiltinLds, kBuiltinSched);
 #if FKS_NPASS == 4
   if (e == hipSuccess) e = raise_lds(mx, kBuiltinDuo);
 #endif
@@ -649,8 +707,13 @@ hipError_t launch_builtin_rows_prof(int fam, int P, int waves, uint32_t* queue, 
   const int key = fam == kRowCompositeW5 || fam == kRowCompositeSplit ? FAM_COMPOSITE_LINEAR : fam;
   return launch_row(kRowsProf, key, dim3(waves), dim3(64), lds, st, a, P, queue, qbase);
 }
+hipError_t launch_builtin_rows_sched(int P, int waves, uint32_t* queue, uint32_t qbase, size_t lds, hipStream_t st,
+                                     const BuiltinArgs& a, SchedRec* rec) {
+  return launch_row(kRowsSched, 0, dim3(waves), dim3(64), lds, st, a, P, queue, qbase, rec);
+}
+int rows_sched_waves_per_cu(size_t lds) { return blocks_per_cu(kRowsSched, 0, 64, lds); }
 template <>
-hipError_t unit_attrs<3, 1>(int mx) { return raise_lds(mx, kRowsProf, kRows); }
+hipError_t unit_attrs<3, 1>(int mx) { return raise_lds(mx, kRowsProf, kRows, kRowsSched); }
 #endif
 
 
@@ -659,7 +722,16 @@ template <>
 hipError_t unit_launch_native<FKS_NPASS>(bool gheap, int P, size_t lds, hipStream_t s, const NativeArgs& a) {
   return launch_row(kNative, gheap, dim3(P), dim3(64), lds, s, a);
 }
+template <>
+hipError_t unit_launch_native_sched<FKS_NPASS>(int P, size_t lds, hipStream_t s, const NativeArgs& a, SchedRec* rec) {
+  return launch_row(kNativeSched, 0, dim3(P), dim3(64), lds, s, a, rec);
+}
 #if FKS_NPASS == 1
+hipError_t launch_native_duo_sched(int P, size_t lds, hipStream_t st, const BuiltinArgs& a, const fksd::RowNativeArgs& nat,
+                                   SchedRec* rec) {
+  return launch_row(kNativeDuoSched, 0, dim3(P), dim3(128), lds, st, a, nat, rec);
+}
+int native_duo_sched_blocks_per_cu(size_t lds) { return blocks_per_cu(kNativeDuoSched, 0, 128, lds); }
 hipError_t launch_native_rows(int P, int waves, int rows_active, uint32_t* queue, uint32_t qbase, size_t lds,
                               hipStream_t st, const BuiltinArgs& a, const fksd::RowNativeArgs& nat) {
   return launch_row(kRowsNative, a.prof != nullptr, dim3(waves), dim3(64), lds, st, a, nat, P, queue, qbase, rows_active);
@@ -690,9 +762,9 @@ hipError_t launch_gm_batch(int fn, const double* x, const double* y, double* out
 #endif
 template <>
 hipError_t unit_attrs<4, FKS_NPASS>(int mx) {
-  hipError_t e = raise_lds(mx, kNative);
+  hipError_t e = raise_lds(mx, kNative, kNativeSched);
 #if FKS_NPASS == 1
-  if (e == hipSuccess) e = raise_lds(mx, kRowsNative, kNativeDuo, kNativeDuoSuite);
+  if (e == hipSuccess) e = raise_lds(mx, kRowsNative, kNativeDuo, kNativeDuoSched, kNativeDuoSuite);
   // (the service kernel's static LDS -- the claim word -- counts against the 160 KiB too)
   if (e == hipSuccess) e = raise_lds(mx - 64, kService);
 #endif
@@ -722,6 +794,12 @@ hipError_t launch_vm(int npass, bool gheap, int P, size_t lds, hipStream_t s, co
 }
 hipError_t launch_native(int npass, bool gheap, int P, size_t lds, hipStream_t s, const NativeArgs& a) {
   return for_npass(npass, [&](auto n) { return unit_launch_native<decltype(n)::value>(gheap, P, lds, s, a); });
+}
+hipError_t launch_builtin_sched(int npass, int P, size_t lds, hipStream_t s, const BuiltinArgs& a, SchedRec* rec) {
+  return for_npass(npass, [&](auto n) { return unit_launch_builtin_sched<decltype(n)::value>(P, lds, s, a, rec); });
+}
+hipError_t launch_native_sched(int npass, int P, size_t lds, hipStream_t s, const NativeArgs& a, SchedRec* rec) {
+  return for_npass(npass, [&](auto n) { return unit_launch_native_sched<decltype(n)::value>(P, lds, s, a, rec); });
 }
 hipError_t set_all_attrs(int max_lds) {
   for (auto unit : {unit_attrs<0, 1>, unit_attrs<0, 2>, unit_attrs<0, 4>, unit_attrs<1, 1>, unit_attrs<1, 2>,

@@ -585,11 +585,13 @@ __device__ __forceinline__ void write_row_result(const RowAcc& acc, int jv, int 
 // FAM == kFamNative: natively compiled programs (`nat`), one per row; only
 // rows < rows_active claim policies, so small batches can run one program per
 // wave (the whole heap in LDS, no other row's divergence in the event loop).
-template <int FAM, class Prof = RowNoProf, bool FLAT = FKS_ROW_FLAT != 0>
+// SCHED (schedule-mode instance): every commit also stores the pod's record
+// into sched[p * n_pods + rank] (device_common.h SchedRec).
+template <int FAM, class Prof = RowNoProf, bool FLAT = FKS_ROW_FLAT != 0, bool SCHED = false>
 __device__ void replay_rows(const DevWorkload& W, const DevWorkload* Wdev, const int32_t* fam, const double* weights,
                             uint64_t* gheap, DevResult* out, int P, uint32_t* queue, uint32_t qbase,
                             uint64_t* prof_out = nullptr, RowNativeArgs nat = RowNativeArgs{nullptr, nullptr, nullptr},
-                            int rows_active = kRowsPerWave, double* table = nullptr) {
+                            int rows_active = kRowsPerWave, double* table = nullptr, SchedRec* sched = nullptr) {
   constexpr bool kNative = FAM == kFamNative;
   const int ra = kNative ? rows_active : kRowsPerWave;
   // W: the kernel-argument copy, read once for the hot scalars below; every
@@ -902,6 +904,9 @@ __device__ void replay_rows(const DevWorkload& W, const DevWorkload* Wdev, const
                       ((uint64_t)best_node << 2) | kDelete;
           if (cold_ptr(Wdev)->trace_hash)
             rcs[0] = mix_event(rcs[0], ((uint64_t)(uint32_t)rank << 2), ((uint64_t)t << 8) ^ (uint64_t)best_node);
+          if constexpr (SCHED) {
+            if (jv == best_node) sched_put(sched + (size_t)p * N + rank, t, best_node, gmask);
+          }
           ecat = 2;
           prof.mark(PH_COMMIT);
         }

@@ -71,6 +71,8 @@ struct SimResult {
   std::vector<double> snap_values;   // 4 per snapshot (record_values)
   std::vector<double> frag_values;   // record_values
   std::vector<int32_t> placement;    // node per pod (-1 never placed; record_placements)
+  std::vector<uint8_t> placement_gpus;    // the pod's GPUs on that node, bit j = GPU j (record_placements)
+  std::vector<int64_t> placement_start;   // time of the creation event that placed it (-1 never placed)
   // record_states: per creation event, [pod, chosen node (-1 failed), cpu_left[N],
   // mem_left[N], gpu_left[N], gmilli_left[G]]
   std::vector<int32_t> states;

@@ -1,7 +1,9 @@
 """L0: entity model, SoA arrays and trace I/O."""
 from .arrays import ClusterArrays, PodArrays, Workload, dense_rank
 from .model import GPU, Cluster, Node, Pod
+from .schedule import Schedule, ScheduleBatch, ScheduleError
 from .traces import TraceParser, TraceSuite, load_default_workload, load_suite, synthetic_workload
 
 __all__ = ["GPU", "Node", "Cluster", "Pod", "ClusterArrays", "PodArrays", "Workload", "dense_rank",
+           "Schedule", "ScheduleBatch", "ScheduleError",
            "TraceParser", "TraceSuite", "load_default_workload", "load_suite", "synthetic_workload"]

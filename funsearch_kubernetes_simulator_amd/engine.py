@@ -121,6 +121,57 @@ def object_engine_eval(code: str, workload: Workload, budget_s: float = 0.0) -> 
             signal.signal(signal.SIGALRM, old)
 
 
+def object_engine_schedule(code: str, workload: Workload, budget_s: float = 0.0):
+    """The object engine's replay with what it left on the pods: (row [13],
+    node [n_pods] int32, GPU mask uint8, start int64).  A replay that raises
+    has its exception code in the row and every pod at -1 / 0 / -1."""
+    import signal
+    import threading
+    from .funsearch.scheduler import FunSearchScheduler
+    from .simulator import DiscreteEventSimulator, KubernetesSimulator, SchedulingEvaluator
+    n = workload.pods.n_pods
+    row = np.zeros(len(COLS))
+    node, mask, start = np.full(n, -1, np.int32), np.zeros(n, np.uint8), np.full(n, -1, np.int64)
+    armed = budget_s > 0 and threading.current_thread() is threading.main_thread()
+    if armed:
+        def _expire(signum, frame):
+            raise ReplayTimeout(f"replay exceeded {budget_s} s")
+        old = signal.signal(signal.SIGALRM, _expire)
+        signal.setitimer(signal.ITIMER_REAL, budget_s)
+    try:
+        sched = FunSearchScheduler(code)
+        cluster, pods = workload.to_objects()
+        ev = SchedulingEvaluator(cluster, enabled=True)
+        sim = KubernetesSimulator(cluster, pods, DiscreteEventSimulator(pods), sched, evaluator=ev)
+        sim.run_schedule()
+        res = ev.get_evaluation_results()
+        score = float(ev.get_policy_score(pods))
+    except Exception as exc:  # any exception aborts the replay: no schedule
+        row[COLS["exc"]] = _exc_code(exc)
+        return row, node, mask, start
+    finally:
+        if armed:
+            signal.setitimer(signal.ITIMER_REAL, 0)
+            signal.signal(signal.SIGALRM, old)
+    index = {nid: i for i, nid in enumerate(workload.cluster.node_ids)}
+    for i, pod in enumerate(pods):
+        if pod.assigned_node == "":
+            continue
+        node[i] = index[pod.assigned_node]
+        mask[i] = sum(1 << int(g) for g in pod.assigned_gpus)
+        start[i] = pod.creation_time
+    row[:9] = (score, res.avg_cpu_utilization, res.avg_memory_utilization, res.avg_gpu_count_utilization,
+               res.avg_gpu_memory_utilization, res.gpu_fragmentation_score, res.num_snapshots,
+               res.num_fragmentation_events, sim.events_processed)
+    row[COLS["n_unplaced"]] = int((node < 0).sum())
+    return row, node, mask, start
+
+
+def _object_schedule_worker(args):
+    code, workload, budget_s = args
+    return object_engine_schedule(code, workload, budget_s)
+
+
 def _exc_code(exc: BaseException) -> int:
     if isinstance(exc, ReplayTimeout):
         return int(Exc.BUDGET)
@@ -240,6 +291,70 @@ class Evaluator:
         from .ops import cpu_engine
         return cpu_engine.simulate_builtin_batch(self.workload, family, weights,
                                                  cpu_engine.SimOptions(**self._cpu_opts()), self.cpu_threads)
+
+    # -- schedules: what each replay did (core/schedule.py) ------------------------------
+    def schedule_family(self, family, weights: np.ndarray):
+        """`ScheduleBatch` of a family batch (`family`: one name, or one per row):
+        the rows of `evaluate_family` and each pod's node, GPUs and start time."""
+        if self.device is not None:
+            return self.device.schedule_builtin(family, weights)
+        from .ops import cpu_engine
+        return cpu_engine.schedule_builtin_batch(self.workload, family, weights,
+                                                 cpu_engine.SimOptions(**self._cpu_opts()), self.cpu_threads)
+
+    def schedule_programs(self, codes: Sequence[str]):
+        """`ScheduleBatch` of program texts, routed as their scores are: the
+        device's native kernels, then -- for programs the JIT declines and rows
+        it defers -- the CPU VM, then the object engine.  Every program gets a
+        schedule, and `engine[i]` says where it came from; a program that
+        raises has its `exc` in its row and nothing placed."""
+        from .core.schedule import ScheduleBatch
+        from .ops import cpu_engine
+        codes = list(codes)
+        compiled = self.compile_batch(codes)
+        n = len(codes)
+        out = ScheduleBatch.empty(n, self.workload.pods.n_pods, list(self.workload.cluster.node_ids))
+        done = [False] * n
+        pending = [i for i, p in enumerate(compiled) if p is not None]
+        if self.device is not None and self.native:
+            exact = getattr(self.device, "math_exact", True)
+            dev_idx = [i for i in pending if compiled[i].device_ok and (exact or not compiled[i].uses_libm)]
+            if dev_idx:
+                got = self.device.schedule_native([compiled[i] for i in dev_idx])
+                for j, i in enumerate(dev_idx):
+                    if not _native_deferred(got.rows[j], self._bump):
+                        out.put([i], got, [j])
+                        done[i] = True
+                        self._bump("device_native", 1)
+        cpu_idx = [i for i in pending if not done[i]]
+        if cpu_idx:
+            got = cpu_engine.schedule_program_batch(self.workload, [compiled[i] for i in cpu_idx],
+                                                    cpu_engine.SimOptions(**self._cpu_opts()), self.cpu_threads)
+            for j, i in enumerate(cpu_idx):
+                row = got.rows[j]
+                if int(row[COLS["exc"]]) in (Exc.UNSUPPORTED, Exc.BUDGET) or row[COLS["inexact"]]:
+                    continue
+                out.put([i], got, [j])
+                done[i] = True
+                self._bump("cpu_vm", 1)
+        rest = [i for i in range(n) if not done[i]]
+        if rest:
+            if self._object_engine_ok():
+                budget_s = float(self.options.get("object_timeout_s", 600.0))
+                jobs = [(codes[i], self.workload, budget_s) for i in rest]
+                if len(rest) > 1 and self.object_workers > 1:
+                    with ProcessPoolExecutor(max_workers=min(self.object_workers, len(rest))) as ex:
+                        results = list(ex.map(_object_schedule_worker, jobs))
+                else:
+                    results = [_object_schedule_worker(j) for j in jobs]
+                for i, (row, node, mask, start) in zip(rest, results):
+                    out.put([i], ScheduleBatch(node[None], mask[None], start[None], row[None], ["object"]))
+                    self._bump("object", 1)
+            else:
+                for i in rest:
+                    out.rows[i, COLS["exc"]] = int(Exc.UNSUPPORTED)
+                    out.engine[i] = "none"
+        return out
 
     # asynchronous form: several family batches in flight (one HIP stream per slot)
     def submit_family(self, slot: int, family: str, weights: np.ndarray) -> None:
@@ -847,6 +962,13 @@ def evaluate(codes, device="auto", workload: Optional[Workload] = None, **option
 def evaluate_detailed(codes: Sequence[str], device="auto", workload: Optional[Workload] = None,
                       **options) -> List[EvalResult]:
     return Evaluator(workload, device, options).evaluate_programs(list(codes))
+
+
+def schedule(codes, device="auto", workload: Optional[Workload] = None, **options):
+    """`ScheduleBatch` of policy programs (one program text or a list of them):
+    each pod's node, GPUs and start time under every program, beside its row."""
+    codes = [codes] if isinstance(codes, str) else list(codes)
+    return Evaluator(workload, device, options).schedule_programs(codes)
 
 
 def copy_workload(w: Workload) -> Workload:

@@ -126,6 +126,40 @@ def simulate_program_batch(w: Workload, progs: Sequence[CompiledPolicy],
                                            threads)
 
 
+# ---------------------------------------------------------------------------- schedules
+def _family_ids(family, count: int) -> np.ndarray:
+    if isinstance(family, str):
+        return np.full(count, FAMILY[family], dtype=np.int32)
+    return np.array([FAMILY[f] for f in family], dtype=np.int32)
+
+
+def _schedule_batch(w: Workload, out, engine: str):
+    from ..core.schedule import ScheduleBatch
+    rows, node, gpus, start = out
+    return ScheduleBatch(node, gpus, start, rows, [engine] * len(rows), list(w.cluster.node_ids))
+
+
+def schedule_builtin_batch(w: Workload, family, weights: np.ndarray, options: Optional[SimOptions] = None,
+                           threads: int = 0):
+    """`ScheduleBatch` of built-in family members: `family` is one name or one
+    per row of `weights` (a mixed batch).  Each pod's node, GPU set and start
+    time, beside the rows `simulate_builtin_batch` returns."""
+    weights = np.ascontiguousarray(weights, dtype=np.float64)
+    weights = weights.reshape(len(weights), -1)
+    out = native().schedule_builtin_batch(native_workload(w), _family_ids(family, len(weights)), weights,
+                                          (options or SimOptions()).as_dict(), threads or default_threads())
+    return _schedule_batch(w, out, "cpu")
+
+
+def schedule_program_batch(w: Workload, progs: Sequence[CompiledPolicy], options: Optional[SimOptions] = None,
+                           threads: int = 0):
+    """`ScheduleBatch` of compiled programs on the CPU VM (rows as `simulate_program_batch`)."""
+    out = native().schedule_program_batch(native_workload(w), [p.code for p in progs], [p.fconst for p in progs],
+                                          [p.iconst for p in progs], [p.ctag for p in progs],
+                                          (options or SimOptions()).as_dict(), threads or default_threads())
+    return _schedule_batch(w, out, "cpu")
+
+
 # ---------------------------------------------------------------------------- native programs on the CPU
 _host_libs: dict = {}
 

@@ -270,6 +270,8 @@ class DeviceEvaluator:
         #: device exp / log / pow == host libm (else programs using them stay on the host)
         self.math_exact = glibc_math_ok()
         self._native_mods: Dict[int, tuple] = {}   # slot -> JIT modules its batch in flight calls into
+        self._sched_jobs: Dict[int, dict] = {}     # slot -> schedule batch in flight (its chunks, `wait_schedule`)
+        self._sched_order: Optional[np.ndarray] = None
         #: the resident program service (start_service): slot -> (P, native rows, first ring index)
         self._svc: Optional[dict] = None
         self._svc_post: Dict[int, Tuple[int, np.ndarray, int, np.ndarray]] = {}   # slot -> (P, rows, first, data slots)
@@ -485,6 +487,94 @@ class DeviceEvaluator:
     def evaluate_builtin(self, family: "str | Sequence[str]", weights: Optional[np.ndarray] = None,
                          n: Optional[int] = None) -> np.ndarray:
         return self._eng.evaluate_builtin(*self._builtin_args(family, weights, n))
+
+    # -- schedules: each pod's node, GPUs and start time (core/schedule.py) ------------------
+    # A schedule launch runs the schedule instances of the replay kernels
+    # (csrc/hip/launch.h): they store one record per placed pod beside the usual
+    # row.  A batch whose records would pass the `schedule_bytes` option
+    # (default 256 MiB per slot) runs in chunks, one after the other.
+    def _schedule_order(self) -> np.ndarray:
+        if getattr(self, "_sched_order", None) is None:
+            self._sched_order = np.argsort(self.workload.pods.pod_rank, kind="stable")   # as prepare_device_workload
+        return self._sched_order
+
+    def _schedule_submit(self, slot: int, job: dict) -> None:
+        lo, hi = job["next"], min(job["next"] + self._eng.schedule_chunk(), job["n"])
+        job["span"] = (lo, hi)
+        job["next"] = hi
+        if job["kind"] == "builtin":
+            self._eng.submit_builtin_schedule(slot, job["fam"][lo:hi], job["W"][lo:hi])
+        else:
+            b, idx = job["batch"], job["idx"][lo:hi]
+            self._eng.submit_native_schedule(slot, b.fn[idx], b.kc, b.koff[idx])
+
+    def submit_schedule_builtin(self, slot: int, family: "str | Sequence[str]", weights: Optional[np.ndarray] = None,
+                                n: Optional[int] = None) -> None:
+        """Start a family schedule batch on `slot`; `wait_schedule(slot)` collects it."""
+        fam, W = self._builtin_args(family, weights, n)
+        job = dict(kind="builtin", fam=fam, W=W, n=len(fam), next=0, rows=[], rec=[])
+        self._schedule_submit(slot, job)
+        self._sched_jobs[slot] = job
+
+    def submit_schedule_native(self, slot: int, progs: Sequence[CompiledPolicy], batch=None) -> None:
+        """Start a program schedule batch on `slot` (a kernel launch of its own,
+        also while the program service runs).  Programs the native backend
+        declines come back as EXC_UNSUPPORTED rows with nothing placed."""
+        if batch is None:
+            batch = self.prepare_native(progs)
+        idx = np.flatnonzero(batch.ok)
+        job = dict(kind="native", batch=batch, idx=idx, n=int(idx.size), total=len(progs), next=0, rows=[], rec=[])
+        try:
+            if idx.size:
+                self._schedule_submit(slot, job)
+        except BaseException:
+            self.native_compiler.release(batch.modules)
+            raise
+        self._sched_jobs[slot] = job
+
+    def wait_schedule(self, slot: int):
+        """The `ScheduleBatch` of the schedule batch in flight on `slot`, in trace pod order."""
+        from ..core.schedule import ScheduleBatch
+        job = self._sched_jobs.pop(slot)
+        node_ids = list(self.workload.cluster.node_ids)
+        try:
+            while job["n"]:
+                rows, rec = self._eng.wait_schedule(slot)
+                job["rows"].append(rows)
+                job["rec"].append(rec)
+                if job["next"] >= job["n"]:
+                    break
+                self._schedule_submit(slot, job)   # the next chunk
+        finally:
+            if job["kind"] == "native":
+                self.native_compiler.release(job["batch"].modules)
+        n_pods = self.workload.pods.n_pods
+        engine = "hip" if job["kind"] == "builtin" else "hip-native"
+        if job["n"]:
+            got = ScheduleBatch.from_ranked(np.concatenate(job["rows"]), np.concatenate(job["rec"]),
+                                            self._schedule_order(), engine, node_ids)
+        if job["kind"] == "builtin":
+            return got
+        out = ScheduleBatch.empty(job["total"], n_pods, node_ids)
+        out.rows[:, 10] = 100.0   # EXC_UNSUPPORTED: not native -> the caller's next engine
+        if job["n"]:
+            out.put(job["idx"], got)
+        return out
+
+    def schedule_builtin(self, family: "str | Sequence[str]", weights: Optional[np.ndarray] = None,
+                         n: Optional[int] = None):
+        """`ScheduleBatch` of a family batch: the rows `evaluate_builtin` returns
+        and each pod's node, GPU mask and start time."""
+        self.submit_schedule_builtin(0, family, weights, n)
+        return self.wait_schedule(0)
+
+    def schedule_native(self, progs: Sequence[CompiledPolicy]):
+        """`ScheduleBatch` of natively compiled programs (rows as `evaluate_native`)."""
+        from ..core.schedule import ScheduleBatch
+        if not progs:
+            return ScheduleBatch.empty(0, self.workload.pods.n_pods, list(self.workload.cluster.node_ids))
+        self.submit_schedule_native(0, progs)
+        return self.wait_schedule(0)
 
     # -- asynchronous slots: several batches in flight on separate HIP streams --------------
     @property
