@@ -73,9 +73,17 @@ constexpr int kRowMaxHeap = (1 << 17) - 2;   // push gathers <= 16 ancestors
 __host__ __device__ inline int row_heap_entries(int n_pods) { return (n_pods + 2 + 63) & ~63; }
 
 // ---- row collectives ---------------------------------------------------------
+// The 16-bit slice of the wave ballot.  Hand it a plain comparison: that one
+// compiles to the v_cmp that writes the lane mask; a condition and-ed together
+// from several (`valid && a < b`) reaches the ballot as a mask of unknown bits
+// in inactive lanes, and is first written out as 0 / 1 per lane and compared
+// again (two more VALU instructions).  The hot callers therefore make lanes
+// that must not vote hold data that fails the comparison.
 __device__ __forceinline__ uint32_t row_ballot(bool p, int rbase) {
   return (uint32_t)(ballot(p) >> rbase) & 0xFFFFu;
 }
+// the same with the higher rows' votes left in bits 16 and up
+__device__ __forceinline__ uint32_t row_ballot_open(bool p, int rbase) { return (uint32_t)(ballot(p) >> rbase); }
 template <int N>
 __device__ __forceinline__ uint32_t row_ror32(uint32_t v) {
   return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x120 + N, 0xF, 0xF, false);
@@ -157,6 +165,73 @@ struct RowHeapT {
     if (c < T) return *reinterpret_cast<const FKS_LDS u64x2*>(top + c + 1);
     return *reinterpret_cast<const FKS_GLOBAL u64x2*>(h + c + 1);
   }
+  // Accesses whose slots lie in a range [LO, HI] known at compile time (a pop
+  // round's four levels, the first scan step): a plain ds_* access when the
+  // whole range is below T, a plain global_* one when it is wholly at or
+  // above T, and the general form (the flat access, or the split variant's
+  // exec-masked pair) only when the range straddles T -- one access
+  // instruction whichever way, and never both sides.  The plain forms need no
+  // generic-address select, and a load counts on its own wait counter alone:
+  // the empty asm after a pair load uses its registers, so the consumer's
+  // wait is placed inside the arm, where an LDS read waits for lgkmcnt only
+  // and leaves the event's global loads in flight.
+  // T is a launch value, wave-uniform: the caller states what it has
+  // established about it, TLO <= T <= THI (nothing: 1 and kMaxTop), and the
+  // arm is fixed at compile time where those bounds decide it; where they
+  // do not, one scalar branch on T picks it.  That test reads T through an
+  // empty asm: left to itself the compiler computes every round's conditions
+  // ahead of the event loop and keeps them as lane masks in spilled SGPRs
+  // (two v_readlane per test).
+  // (The asm texts of the three arms differ, or their copies merge behind the join.)
+  static constexpr int kMaxTop = (160 << 10) / 8 - 1;   // no T beyond the CU's LDS
+  __device__ __forceinline__ int top_here() const {
+    int t = T;
+    asm volatile("" : "+s"(t));
+    return t;
+  }
+  enum Arm { kArmLds, kArmHbm, kArmEither };
+  template <int LO, int HI, int TLO, int THI>
+  __device__ __forceinline__ Arm arm_of() const {
+    if constexpr (HI < TLO) return kArmLds;
+    else if constexpr (LO >= THI) return kArmHbm;
+    else if constexpr (LO < TLO && HI >= THI) return kArmEither;
+    else {
+      const int t = top_here();
+      if (HI < t) return kArmLds;
+      if (LO >= TLO && LO >= t) return kArmHbm;
+      return kArmEither;
+    }
+  }
+  template <int LO, int HI, int TLO = 1, int THI = kMaxTop>
+  __device__ __forceinline__ u64x2 ld_pair_in(int c) const {   // slots c, c + 1 in [LO, HI]
+    u64x2 r;
+    const Arm a = arm_of<LO, HI, TLO, THI>();
+    if (a == kArmLds) {
+      r = *reinterpret_cast<const FKS_LDS u64x2*>(top + c + 1);
+      asm volatile("; settled: lds" : "+v"(r));
+    } else {
+      if (a == kArmHbm) {
+        r = *reinterpret_cast<const FKS_GLOBAL u64x2*>(h + c + 1);
+        asm volatile("; settled: hbm" : "+v"(r));
+      } else {
+        r = ld_pair(c);
+        asm volatile("; settled: either" : "+v"(r));
+      }
+    }
+    return r;
+  }
+  template <int LO, int HI, int TLO = 1, int THI = kMaxTop>
+  __device__ __forceinline__ void st_in(int i, uint64_t v) const {
+    const Arm a = arm_of<LO, HI, TLO, THI>();
+    if (a == kArmLds) {
+      top[i + 1] = v;
+    } else {
+      if (a == kArmHbm) h[i + 1] = v;
+      else st(i, v);
+    }
+  }
+  // the root: T >= 1 in every launch (engine_host row_layout and the native layouts)
+  __device__ __forceinline__ uint64_t root() const { return top[1]; }
   // bit `pos` of the deletion bitmap := (v is a DELETION): one LDS masked-OR
   // atomic (word = (word & ~bit) | data), safe when several lanes of the row
   // hit the same word in one instruction.  LDS operations of a wave complete
@@ -185,48 +260,92 @@ struct RowHeapT {
     // the round holding it moves the entries before it and places `last` on
     // its parent, and the walk stops there -- the entries below keep their
     // slots, exactly as after CPython's full descent and bubble-up.
-    constexpr int kRounds = 5;   // 20 levels (host guarantees n < 2^17)
+    // A round that goes on descended four levels, so round RD starts at depth
+    // 4 RD: its subtree nodes (the slots it stores to) and their child pairs
+    // (the slots it loads) lie in ranges fixed per round -- ld_pair_in / st_in.
+    // The heap tops the host chooses itself (engine_host row_layout: 63 or
+    // 127) fix every round's arm -- round 0 in LDS, round 1 across T, rounds 2
+    // and later in HBM -- so one test per pop selects a walk compiled for
+    // them; any other T (the row_heap_top option, the native layouts) takes
+    // the walk that tests T at each access.
+    const int t = top_here();
+    if (t >= kHostTopLo && t <= kHostTopHi) pop_walk<kHostTopLo, kHostTopHi>(n, last, k, ki);
+    else pop_walk<1, kMaxTop>(n, last, k, ki);
+  }
+  static constexpr int kHostTopLo = 63, kHostTopHi = 127;
+  template <int TLO, int THI>
+  __device__ __forceinline__ void pop_walk(int n, uint64_t last, int k, int ki) const {
     int pos = 0, target = -1;
-#pragma unroll
-    for (int rd = 0; rd < kRounds; ++rd) {
-      if (2 * pos + 1 >= n) break;   // pos is a leaf
-      const int q = ((pos + 1) << k) - 1 + ki;
-      const int c = 2 * q + 1;
-      const bool valid = j < 15 && c < n;
-      uint64_t vl = ~0ull, vr = ~0ull;
-      if (valid) {
-        const u64x2 pr = ld_pair(c);
-        vl = pr.x;
-        vr = pr.y;
-      }
-      const bool go_r = valid && (c + 1 < n) && !(vl < vr);
-      const uint32_t m = row_ballot(go_r, rbase);
-      // node j is on the path iff every ancestor in the subtree chooses the
-      // child towards j (lane constants anc / dir), and it is a path *parent*
-      // iff it has children itself: no serial walk.  (A valid node's
-      // ancestors are valid: their child pairs sit at smaller heap indices.)
-      const bool on = valid && ((m ^ dir) & anc) == 0;
-      const uint32_t onm = row_ballot(on, rbase);
-      const uint64_t v = go_r ? vr : vl;
-      const uint32_t g = row_ballot(on && last < v, rbase);
-      const int jl = g ? __ffs(g) - 1 : kRow;
-      if (on && j < jl) {   // moves up one level
-        st(q, v);
-        mark(q, v);
-      }
-      if (g) {   // `last` lands on the slot of the first path entry greater than it
-        target = row_read(q, rbase, jl);
-        break;
-      }
-      // the deepest path parent jd hands over its chosen child (the new path
-      // end) and its depth in the subtree (levels descended this round - 1)
-      const int jd = 31 - __clz(onm);
-      const int nk = row_read(((c + (int)go_r) << 2) | k, rbase, jd);
-      pos = nk >> 2;
-      if ((nk & 3) < 3) break;   // reached a leaf
-    }
+    // 5 rounds = 20 levels (host guarantees n < 2^17)
+    (void)(pop_round<0, TLO, THI>(n, last, k, ki, pos, target) && pop_round<1, TLO, THI>(n, last, k, ki, pos, target) &&
+           pop_round<2, TLO, THI>(n, last, k, ki, pos, target) && pop_round<3, TLO, THI>(n, last, k, ki, pos, target) &&
+           pop_round<4, TLO, THI>(n, last, k, ki, pos, target));
     if (target < 0) target = pos;
-    if (j == 0) { st(target, last); mark(target, last); }
+    // Lane 0 places `last`; lane 1 fills the slot it came from, slot n, with
+    // ~0, so that between pops the slots from n up to the heap's first size
+    // hold ~0 (begin() fills the first one; a push overwrites slot n and
+    // nothing beyond).  During the walk slot n still holds `last` itself, and
+    // the parent of a missing right child (c + 1 = n) reads it as that child:
+    //   * `last` > its left child: the left child wins, as if slot n held ~0;
+    //   * `last` < its left child, and an earlier path entry is greater than
+    //     `last` too: the round ends at that entry, this parent stores nothing;
+    //   * `last` < its left child, and no earlier entry is greater: the walk
+    //     without slot n would end here and place `last` on this parent.  Here
+    //     the "right child" wins instead: the round moves it up -- which stores
+    //     `last` on this parent -- and hands on slot n as the path end, a leaf,
+    //     so the walk ends with target = n.
+    // In the last case `last` is already in place and lane 0 writes ~0 as well:
+    // both lanes then store the same value to slot n, and no result depends on
+    // which lane of a store instruction wins an address.
+    static_assert(!MAP, "the ~0 fill is not marked");
+    if (j < 2) st(j == 0 ? target : n, j == 0 && target != n ? last : ~0ull);
+  }
+  // one round of pop_reinsert from the path end `pos` (depth 4 RD); false: the walk is over
+  template <int RD, int TLO, int THI>
+  __device__ __forceinline__ bool pop_round(int n, uint64_t last, int k, int ki, int& pos, int& target) const {
+    constexpr int kQlo = (1 << (4 * RD)) - 1, kQhi = (1 << (4 * RD + 4)) - 2;   // subtree nodes
+    constexpr int kClo = 2 * kQlo + 1, kChi = 2 * kQhi + 2;                      // their children
+    if (2 * pos + 1 >= n) return false;   // pos is a leaf
+    const int q = RD == 0 ? j : ((pos + 1) << k) - 1 + ki;   // (round 0: pos = 0, node j itself)
+    const int c = 2 * q + 1;
+    const bool valid = j < 15 && c < n;
+    uint64_t vl = ~0ull, vr = ~0ull;
+    if (valid) {
+      const u64x2 pr = ld_pair_in<kClo, kChi, TLO, THI>(c);
+      vl = pr.x;
+      vr = pr.y;
+    }
+    // the right child wins when it is the smaller: keys are distinct, a lane
+    // without a pair holds ~0 twice, and no bound test guards a missing right
+    // child (c + 1 = n): slot n holds `last` for the time of the walk, which
+    // pop_walk's closing comment shows to give the same heap -- one comparison
+    const bool go_r = vr < vl;
+    const uint32_t m = row_ballot_open(go_r, rbase);   // (anc has no bit from 15 up)
+    const uint64_t v = go_r ? vr : vl;
+    const uint32_t ltm = row_ballot(last < v, rbase);
+    // node j is on the path iff every ancestor in the subtree chooses the
+    // child towards j (lane constants anc / dir), and it is a path *parent*
+    // iff it has children itself: no serial walk.  (A valid node's
+    // ancestors are valid: their child pairs sit at smaller heap indices.)
+    // A lane without children compares against a value the left side never takes.
+    const bool on = ((m ^ dir) & anc) == (valid ? 0u : ~0u);
+    const uint32_t onm = row_ballot(on, rbase);
+    const uint32_t g = onm & ltm;   // path parents whose chosen child is greater than `last`
+    const int jl = g ? __ffs(g) - 1 : kRow;
+    if (on && j < jl) {   // moves up one level
+      st_in<kQlo, kQhi, TLO, THI>(q, v);
+      mark(q, v);
+    }
+    if (g) {   // `last` lands on the slot of the first path entry greater than it
+      target = row_read(q, rbase, jl);
+      return false;
+    }
+    // the deepest path parent jd hands over its chosen child (the new path
+    // end) and its depth in the subtree (levels descended this round - 1)
+    const int jd = 31 - __clz(onm);
+    const int nk = row_read(((c + (int)go_r) << 2) | k, rbase, jd);
+    pos = nk >> 2;
+    return (nk & 3) == 3;   // fewer than four levels: reached a leaf
   }
 
   // CPython heappush on a heap of n items
@@ -235,7 +354,7 @@ struct RowHeapT {
     const int anc = ((n + 1) >> l) - 1;
     const bool valid = n > 0 && anc >= 0;
     const uint64_t v = valid ? ld(anc) : 0;
-    const bool gt = valid && item < v;
+    const bool gt = item < v;   // (a lane without an ancestor holds 0: never greater)
     const int J = __popc(row_ballot(gt, rbase));
     const int dst = ((n + 1) >> (l - 1)) - 1;
     if (gt) { st(dst, v); mark(dst, v); }
@@ -278,11 +397,21 @@ struct RowHeapT {
     // while base - 1 < n -- on this lane's slots c = base + 2j - 1 and c + 1
     // (c odd; -1: the padding), while c < n + 2j
     const int lim = n + 2 * j;
-    for (int c = 2 * j - 1; c < lim; c += 2 * kRow) {
-      u64x2 pr = {0, 0};
-      if (c < n) pr = ld_pair(c);       // (c + 1 <= n <= N: inside the heap's allocation)
-      const bool d0 = c >= 0 && c < n && ((uint32_t)pr.x & 3u) == (uint32_t)kDelKind;
-      const bool d1 = c + 1 < n && ((uint32_t)pr.y & 3u) == (uint32_t)kDelKind;
+    // the first step always runs (-1 < n) and is where most scans end: its
+    // slots -1 .. 30 are read by level (ld_pair_in), the later steps' as they lie
+    int c = 2 * j - 1;
+    u64x2 pr = {0, 0};
+    if (c < n) pr = ld_pair_in<-1, 2 * kRow - 2>(c);   // (c + 1 <= n <= N: inside the heap's allocation)
+    for (;;) {
+      // plain comparisons (row_ballot): a lane past the heap holds zeros, the
+      // padding at address 0 is zero (the host's image; nothing stores there),
+      // and slot n, read when c + 1 = n, holds ~0 -- none is a deletion.  One
+      // exception: the pop that empties the heap skips pop_reinsert, so with
+      // n = 0 slot 0 still holds the event just popped; that event is the
+      // creation whose placement failed, never a deletion.
+      static_assert(kDelKind != 0 && kDelKind != 3, "0 and ~0 must not read as deletions");
+      const bool d0 = ((uint32_t)pr.x & 3u) == (uint32_t)kDelKind;
+      const bool d1 = ((uint32_t)pr.y & 3u) == (uint32_t)kDelKind;
       const uint32_t b0 = row_ballot(d0, rbase);
       const uint32_t b = b0 | row_ballot(d1, rbase);
       if (b) {
@@ -292,8 +421,11 @@ struct RowHeapT {
               (uint32_t)row_read((int)(uint32_t)mine, rbase, fl);
         return c - 2 * j + 1 + 2 * fl - (int)((b0 >> fl) & 1u);
       }
+      c += 2 * kRow;
+      if (c >= lim) return -1;
+      pr = u64x2{0, 0};
+      if (c < n) pr = ld_pair(c);
     }
-    return -1;
   }
 };
 using RowHeap = RowHeapT<>;
@@ -694,7 +826,13 @@ __device__ void replay_rows(const DevWorkload& W, const DevWorkload* Wdev, const
     }
     const int words = row_heap_entries(N) / 2;   // 16-byte pairs of the shifted heap
     for (int i = jv; i < words; i += kRow) {
-      const u64x2 v = heap_src[i];
+      u64x2 v = heap_src[i];
+      // slot N (address N + 1), just behind the last entry, starts as ~0, and
+      // every slot a pop vacates becomes ~0 at the end of its walk
+      // (RowHeapT::pop_walk): between pops the slots from n up hold ~0, which
+      // scan_deletion relies on; what a walk itself reads there is argued in pop_walk
+      if (2 * i == N + 1) v.x = ~0ull;
+      if (2 * i == N) v.y = ~0ull;
       if constexpr (FLAT) {
         // through the generic addresses the event loop uses (no separate
         // LDS / HBM pointers held live across the loop)
@@ -745,7 +883,7 @@ __device__ void replay_rows(const DevWorkload& W, const DevWorkload* Wdev, const
     int ecat = 0;   // (profiled build: the event's kind for the wave-step histogram)
     do {   // one event; `break` = abort the replay (exc set) or end of the event
       // ---------------- pop
-      const uint64_t top = heap.ld(0);
+      const uint64_t top = heap.root();
       const int rank = (int)((top >> lb) & ((1ull << rb) - 1));
       typedef int v4i __attribute__((ext_vector_type(4)));
       const v4i precv = *reinterpret_cast<const FKS_GLOBAL v4i*>(global_ptr(&W.pod[rank]));
