@@ -338,6 +338,8 @@ SimResult simulate(const Workload& w, Scorer& scorer, const SimOptions& opt) {
         }
         assigned[p] = n;
         if (opt.record_placements) start[p] = ev.time;
+        if (opt.record_time)
+          record_time_metrics(res.time, ev.time, w.pctime[p], w.pdur[p], w.pcpu[p], w.pmem[p], w.pngpu[p], w.pgmilli[p]);
         if (waiting[p]) {
           waiting[p] = 0; --waiting_count;
           if (w.pngpu[p] > 0) {

@@ -357,6 +357,64 @@ PYBIND11_MODULE(_fks_cpu, m) {
   }, py::arg("workload"), py::arg("codes"), py::arg("fconsts"), py::arg("iconsts"), py::arg("ctags"),
      py::arg("options") = py::dict(), py::arg("threads") = 1);
 
+  // Time metrics of a batch, threaded like the batch calls above: (rows [P, 13],
+  // records [P, 24] int64 -- fks::TimeRec: 8 slots, then the 32 buckets as 16
+  // words of two).  A replay that raises reports an all-zero record.
+  m.def("time_builtin_batch", [](const Workload& w, py::array_t<int32_t, py::array::c_style | py::array::forcecast> fam,
+                                 py::array_t<double, py::array::c_style | py::array::forcecast> weights,
+                                 py::dict opts, int threads) {
+    const int64_t P = fam.size(), K = weights.ndim() > 1 ? weights.shape(1) : 0;
+    if (weights.ndim() != 2 || weights.shape(0) != P) throw std::invalid_argument("weights must be [P, K] float64");
+    SimOptions o = make_options(opts);
+    o.record_time = true;
+    py::array_t<double> rows({P, (int64_t)kCols});
+    py::array_t<int64_t> rec({P, (int64_t)(sizeof(TimeRec) / 8)});
+    double* rp = rows.mutable_data();
+    int64_t* tp = rec.mutable_data();
+    const int32_t* fp = fam.data();
+    const double* wp = weights.data();
+    {
+      py::gil_scoped_release rel;
+      parallel_for(P, threads, [&](int64_t i) {
+        BuiltinScorer sc; sc.family = fp[i];
+        for (int64_t k = 0; k < K && k < 16; ++k) sc.w[k] = wp[i * K + k];
+        const SimResult r = simulate(w, sc, o);
+        fill_row(rp + i * kCols, r);
+        const TimeRec t = r.exc == EXC_NONE ? r.time : TimeRec{};
+        std::memcpy(tp + i * (sizeof(TimeRec) / 8), &t, sizeof(TimeRec));
+      });
+    }
+    return py::make_tuple(rows, rec);
+  }, py::arg("workload"), py::arg("families"), py::arg("weights"), py::arg("options") = py::dict(), py::arg("threads") = 1);
+
+  m.def("time_program_batch", [](const Workload& w, std::vector<py::bytes> codes,
+                                 std::vector<std::vector<double>> fconsts,
+                                 std::vector<std::vector<int64_t>> iconsts,
+                                 std::vector<std::vector<uint8_t>> ctags, py::dict opts, int threads) {
+    const int64_t P = (int64_t)codes.size();
+    std::vector<Program> progs;
+    for (int64_t i = 0; i < P; ++i) progs.push_back(make_program(std::string(codes[i]), fconsts[i], iconsts[i], ctags[i]));
+    SimOptions o = make_options(opts);
+    o.record_time = true;
+    py::array_t<double> rows({P, (int64_t)kCols});
+    py::array_t<int64_t> rec({P, (int64_t)(sizeof(TimeRec) / 8)});
+    double* rp = rows.mutable_data();
+    int64_t* tp = rec.mutable_data();
+    {
+      py::gil_scoped_release rel;
+      parallel_for(P, threads, [&](int64_t i) {
+        VmScorer sc(progs[i], o.budget);
+        SimResult r = simulate(w, sc, o);
+        if (r.exc == EXC_NONE && sc.exc) r.exc = sc.exc;
+        fill_row(rp + i * kCols, r);
+        const TimeRec t = r.exc == EXC_NONE ? r.time : TimeRec{};
+        std::memcpy(tp + i * (sizeof(TimeRec) / 8), &t, sizeof(TimeRec));
+      });
+    }
+    return py::make_tuple(rows, rec);
+  }, py::arg("workload"), py::arg("codes"), py::arg("fconsts"), py::arg("iconsts"), py::arg("ctags"),
+     py::arg("options") = py::dict(), py::arg("threads") = 1);
+
   m.def("simulate_native_batch", [](const Workload& w, std::vector<uint64_t> fns,
                                     py::array_t<int64_t, py::array::c_style | py::array::forcecast> kc,
                                     py::array_t<int32_t, py::array::c_style | py::array::forcecast> koff,

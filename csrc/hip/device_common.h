@@ -72,6 +72,69 @@ struct SchedSink {
   SchedRec* rec;   // the policy's n_pods records
 };
 
+// Time-metrics mode (separate kernel instances, launch.h): one record per
+// policy over the pods its replay placed -- how long they waited (start minus
+// the pod's creation time), when the last one ends, the resource-seconds they
+// hold and a histogram of the waits by bit length.  Every placed pod is later
+// deleted, so busy[] is the time integral of the cluster's usage.  All integer:
+// the host gates the workload so that no sum can pass 2^63.  A replay that
+// raises writes an all-zero record.  (Host twin: fks/time_rec.hpp.)
+struct TimeRec {
+  int64_t wait_sum;    // slot 0
+  int64_t wait_max;    // slot 1 (0 if none placed)
+  int64_t end_max;     // slot 2: max start + dur (0 if none placed)
+  int64_t busy[4];     // slots 3-6: sum cpu*dur, mem*dur, ngpu*dur, ngpu*gmilli*dur
+  int64_t n_placed;    // slot 7
+  uint32_t hist[32];   // hist[b]: pods with bit_length(wait) == b, clamped at 31
+};
+static_assert(sizeof(TimeRec) == 192, "eight 64-bit slots and 32 buckets");
+constexpr int kTimeSlots = 8;
+// The accumulators of one replay, spread over lanes: the lane whose index in
+// its group is j holds slot j (j < 8) in `slot`.  ROW (16-lane groups): buckets
+// j and j + 16 in h0 / h1; otherwise (a 64-lane wave) bucket j in h0.  commit()
+// takes group-uniform values and every lane picks its own addend: no
+// cross-lane operation, no LDS, no atomics.
+template <bool ROW>
+struct TimeAcc {
+  int64_t slot;
+  uint32_t h0, h1;
+  __device__ __forceinline__ void init() { slot = 0; h0 = h1 = 0u; }
+  // wait >= 0, t + dur >= 0 (the commit site has checked it), all demands >= 0 (host gate)
+  __device__ __forceinline__ void commit(int j, int64_t wait, int64_t end, int cpu, int mem, int ngpu, int gmilli,
+                                         int dur) {
+    const uint32_t x = j == 3 ? (uint32_t)cpu : j == 4 ? (uint32_t)mem : j == 5 ? (uint32_t)ngpu
+                       : j == 6 ? (uint32_t)(ngpu * gmilli) : 0u;   // ngpu < 2^8, gmilli < 2^16
+    const int64_t c = j == 0 ? wait : j == 7 ? 1 : 0;
+    const int64_t add = (int64_t)((uint64_t)x * (uint32_t)dur) + c;
+    const int64_t v = j == 1 ? wait : end;
+    const int64_t mx = slot > v ? slot : v;
+    slot = (j == 1 || j == 2) ? mx : slot + add;
+    const int b = wait == 0 ? 0 : 64 - __builtin_clzll((unsigned long long)wait);
+    const int bc = b < 31 ? b : 31;
+    h0 += j == bc ? 1u : 0u;
+    if constexpr (ROW) h1 += j + 16 == bc ? 1u : 0u;
+  }
+  // plain vector stores; `ok` false (the replay raised): zeros
+  __device__ __forceinline__ void write(TimeRec* rec, int j, bool ok) const {
+    FKS_GLOBAL int64_t* s = reinterpret_cast<FKS_GLOBAL int64_t*>(global_ptr(rec));
+    FKS_GLOBAL uint32_t* h = reinterpret_cast<FKS_GLOBAL uint32_t*>(s + kTimeSlots);
+    if (j < kTimeSlots) s[j] = ok ? slot : 0;
+    if constexpr (ROW) {
+      if (j < 16) { h[j] = ok ? h0 : 0u; h[j + 16] = ok ? h1 : 0u; }
+    } else {
+      if (j < 32) h[j] = ok ? h0 : 0u;
+    }
+  }
+};
+// The time sink of the one-wave replay (replay.hip.h): NoTime compiles to nothing.
+struct NoTime {
+  static constexpr bool kOn = false;
+};
+struct TimeSink {
+  static constexpr bool kOn = true;
+  TimeRec* rec;   // the policy's record
+};
+
 __device__ __forceinline__ int uni(int x) { return __builtin_amdgcn_readfirstlane(x); }
 __device__ __forceinline__ uint32_t uni(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
 __device__ __forceinline__ int64_t uni64(int64_t x) {

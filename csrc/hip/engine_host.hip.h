@@ -186,6 +186,8 @@ struct Slot {
   DevBuf res, tab, fam, w, code, meta, kpay, ktag, gheap, prof, queue, kc;
   DevBuf sched;         // schedule launches: [P, n_pods] SchedRec, reserved on first use
   int sched_P = 0;      // policies of the schedule batch in flight (0: an ordinary batch)
+  DevBuf trec;          // time-metrics launches: [P] TimeRec, reserved on first use
+  int time_P = 0;       // policies of the time-metrics batch in flight (0: none)
   HostBuf h_in, h_tab;
   bool fused_table = false;   // the launch wrote h_tab itself (row kernels)
   int P = 0;
@@ -194,7 +196,7 @@ struct Slot {
   bool busy = false;
   roctx_range_id_t range = 0;   // roctx range spanning submit -> wait (rocprofv3 --marker-trace)
   void release() {
-    for (DevBuf* b : {&res, &tab, &fam, &w, &code, &meta, &kpay, &ktag, &gheap, &prof, &queue, &kc, &sched}) b->release();
+    for (DevBuf* b : {&res, &tab, &fam, &w, &code, &meta, &kpay, &ktag, &gheap, &prof, &queue, &kc, &sched, &trec}) b->release();
     h_in.release();
     h_tab.release();
     if (done) (void)hipEventDestroy(done);
@@ -275,6 +277,7 @@ class DeviceEngine {
     W_.used_gcnt0 = geti("used_gcnt"); W_.used_gmilli0 = geti("used_gmilli");
     W_.rank_bits = (int32_t)geti("rank_bits"); W_.node_bits = (int32_t)geti("node_bits");
     W_.low_bits = (int32_t)geti("low_bits"); W_.time_bits = (int32_t)geti("time_bits");
+    if (d.contains("time_ok")) time_ok_ = d["time_ok"].cast<bool>();
     W_.snapshot_interval = 0.05;
     W_.trace_hash = 1;
     prepare_recips(d);
@@ -545,10 +548,88 @@ class DeviceEngine {
     return py::make_tuple(rows, rec);
   }
 
+  // ---- time-metrics mode: one TimeRec per replay, beside its row --------------------------
+  // A time batch runs on the time instances (launch.h): the composite or the
+  // mixed-family row kernel / the mixed-family HBM-heap wave kernel / the
+  // two-wave or HBM-heap native kernel.  wait_time(slot) returns the rows and
+  // the records [P, 24] int64 (TimeRec: 8 slots, then the 32 buckets as 16
+  // words of two).  192 bytes per policy: no chunking.
+  void time_guard(int P) const {
+    if (P < 1) throw std::invalid_argument("empty batch");
+    if (!time_ok_)
+      throw std::invalid_argument("time mode: a sum over this workload's pods could pass 2^63 (or a duration or demand "
+                                  "is negative)");
+    if (W_.check_every > 0)
+      throw std::invalid_argument("time mode and check_invariants cannot be combined: the time instances carry no "
+                                  "invariant check (set check_invariants to 0)");
+  }
+  TimeRec* time_begin(Slot& s, int P) {
+    s.trec.reserve((size_t)P * sizeof(TimeRec));
+    return s.trec.as<TimeRec>();
+  }
+
+  void submit_builtin_time(int slot, py::array_t<int32_t, py::array::c_style | py::array::forcecast> fam,
+                           py::array_t<double, py::array::c_style | py::array::forcecast> weights) {
+    Slot& s = idle_slot(slot);
+    const int P = (int)fam.size();
+    if (weights.ndim() != 2 || weights.shape(0) != P || weights.shape(1) != kWeights)
+      throw std::invalid_argument("weights must be [P, 16] float64");
+    time_guard(P);
+    HIP_OK(hipSetDevice(device_));
+    s.range = roctxRangeStartA("fks.batch.builtin.time");
+    stage_builtin(s, fam.data(), weights.data(), P);
+    if (s.fam_spec != FAM_COMPOSITE_LINEAR || !use_rows()) s.fam_spec = -1;   // composite rows, or the mixed instance
+    {
+      py::gil_scoped_release rel;
+      TimeRec* trec = time_begin(s, P);
+      if (use_rows()) {
+        last_time_instance_ = s.fam_spec == FAM_COMPOSITE_LINEAR ? "rows_composite" : "rows_mixed";
+        launch_rows(s, false, nullptr, trec);
+      } else {
+        const DevWorkload Wl = launch_workload(true, 0, false);
+        const size_t lds = lds_bytes(true, Wl.heap_top, 0);
+        if (lds > kMaxLds) throw std::invalid_argument("replay layout exceeds the 160 KiB LDS");
+        const size_t wb = (size_t)P * kWeights * 8;
+        const fksk::BuiltinArgs a{Wl, nullptr, reinterpret_cast<const int32_t*>(s.h_in.dev<char>() + wb),
+                                  s.h_in.dev<double>(), s.w.as<double>(), s.res.as<DevResult>(), gheap_for(s, P), nullptr};
+        last_time_instance_ = "wave_mixed";
+        HIP_OK(fksk::launch_builtin_time(npass_, P, lds, s.stream, a, trec));
+      }
+      finish(s);
+    }
+    s.time_P = P;
+  }
+
+  void submit_native_time(int slot, py::array_t<uint64_t, py::array::c_style | py::array::forcecast> fn,
+                          py::array_t<int64_t, py::array::c_style | py::array::forcecast> kc,
+                          py::array_t<int32_t, py::array::c_style | py::array::forcecast> koff) {
+    time_guard((int)fn.size());
+    submit_native_impl(slot, fn, kc, koff, false, false, true);
+    slot_at(slot).time_P = (int)fn.size();
+  }
+
+  py::tuple wait_time(int slot) {
+    Slot& s = slot_at(slot);
+    if (!s.busy || s.time_P != s.P || s.P < 1) throw std::invalid_argument("slot has no time batch in flight");
+    const int P = s.P;
+    py::array_t<double> rows = wait(slot);
+    py::array_t<int64_t> rec({(py::ssize_t)P, (py::ssize_t)(sizeof(TimeRec) / 8)});
+    int64_t* dst = rec.mutable_data();
+    {
+      // after the slot's event: the records come back on its stream
+      py::gil_scoped_release rel;
+      HIP_OK(hipSetDevice(device_));
+      HIP_OK(hipMemcpyAsync(dst, s.trec.p, (size_t)P * sizeof(TimeRec), hipMemcpyDeviceToHost, s.stream));
+      HIP_OK(hipStreamSynchronize(s.stream));
+    }
+    s.time_P = 0;
+    return py::make_tuple(rows, rec);
+  }
+
   void submit_native_impl(int slot, py::array_t<uint64_t, py::array::c_style | py::array::forcecast> fn,
                           py::array_t<int64_t, py::array::c_style | py::array::forcecast> kc,
                           py::array_t<int32_t, py::array::c_style | py::array::forcecast> koff, bool profiled,
-                          bool schedule = false) {
+                          bool schedule = false, bool timed = false) {
     Slot& s = idle_slot(slot);
     const int P = (int)fn.size();
     if (P < 1) throw std::invalid_argument("empty batch");
@@ -577,12 +658,13 @@ class DeviceEngine {
     {
       py::gil_scoped_release rel;
       SchedRec* rec = schedule ? schedule_begin(s, P) : nullptr;
+      TimeRec* trec = timed ? time_begin(s, P) : nullptr;
       if (use_rows()) {
-        launch_rows_native(s, P, fb, kc_dev, profiled, rec);
+        launch_rows_native(s, P, fb, kc_dev, profiled, rec, trec);
         finish(s);
         return;
       }
-      const bool g = schedule || use_gheap_native(P);   // (the schedule instance: HBM heap)
+      const bool g = schedule || timed || use_gheap_native(P);   // (the schedule and time instances: HBM heap)
       // kKcLds / 64 VM-register rows of LDS hold the policy's constant block
       const DevWorkload Wl = launch_workload(g, kKcLds / kWave, false);
       const size_t lds = lds_bytes(g, Wl.heap_top, kKcLds / kWave);
@@ -590,8 +672,10 @@ class DeviceEngine {
       uint64_t* gh = g ? gheap_for(s, P) : nullptr;
       const fksk::NativeArgs a{Wl, nullptr, s.h_in.dev<const uint64_t>(), kc_dev,
                                reinterpret_cast<const int32_t*>(s.h_in.dev<char>() + fb), s.res.as<DevResult>(), gh};
-      HIP_OK(rec ? fksk::launch_native_sched(npass_, P, lds, s.stream, a, rec)
-                 : fksk::launch_native(npass_, g, P, lds, s.stream, a));
+      if (trec) last_time_instance_ = "wave_native";
+      HIP_OK(trec  ? fksk::launch_native_time(npass_, P, lds, s.stream, a, trec)
+             : rec ? fksk::launch_native_sched(npass_, P, lds, s.stream, a, rec)
+                   : fksk::launch_native(npass_, g, P, lds, s.stream, a));
       finish(s);
     }
   }
@@ -968,6 +1052,7 @@ class DeviceEngine {
     d["row_composite_waves"] = comp_waves_;
     d["stack_bytes"] = (int64_t)stack_bytes_;
     d["row_flat"] = row_flat_;
+    d["time_instance_last"] = last_time_instance_;
     d["native_rows_last"] = last_native_rows_;
     d["native_rows_top_last"] = last_native_top_;   // heap top of the last native-program row launch
     d["native_waves_last"] = last_native_waves_;
@@ -1220,6 +1305,7 @@ class DeviceEngine {
     s.w.reserve(sizeof(double) * kWeights * (size_t)P);
     s.P = P;
     s.sched_P = 0;
+    s.time_P = 0;
   }
 
   // numpy -> pinned staging -> device (async on the slot's stream)
@@ -1299,7 +1385,8 @@ class DeviceEngine {
 
   // row kernel launch (optionally the phase-profiled build); returns the wave count
   // rec: the schedule instance (mixed family) and its record buffer
-  int launch_rows(Slot& s, bool profiled, SchedRec* rec = nullptr) {
+  // trec: the time instance (composite when the batch is, else mixed) and its record buffer
+  int launch_rows(Slot& s, bool profiled, SchedRec* rec = nullptr, TimeRec* trec = nullptr) {
     const int P = s.P;
     DevWorkload Wl = W_;
     const int kf = s.fam_spec != FAM_COMPOSITE_LINEAR ? s.fam_spec
@@ -1309,6 +1396,8 @@ class DeviceEngine {
     std::pair<int, int> lay = row_layout(kf);
     if (rec)   // the layout of the mixed instance; residency as the schedule instance's registers allow
       lay.second = std::max(1, std::min(lay.second, fksk::rows_sched_waves_per_cu(rows_lds_bytes(W_.n_pods, lay.first))));
+    if (trec)   // the layout of the instance it was made from; residency as the time instance's registers allow
+      lay.second = std::max(1, std::min(lay.second, fksk::rows_time_waves_per_cu(s.fam_spec, rows_lds_bytes(W_.n_pods, lay.first))));
     Wl.heap_top = lay.first;
     const size_t lds = std::max(rows_lds_bytes(W_.n_pods, Wl.heap_top) + (profiled ? kRowProfBytes : 0), row_min_lds_);
     if (lds > kMaxLds) throw std::invalid_argument("row kernel layout exceeds the 160 KiB LDS");
@@ -1326,7 +1415,8 @@ class DeviceEngine {
                               s.h_in.dev<double>(), s.w.as<double>(), s.res.as<DevResult>(), s.gheap.as<uint64_t>(),
                               profiled ? s.prof.as<uint64_t>() : nullptr, s.h_tab.dev<double>()};
     s.fused_table = true;
-    if (rec) HIP_OK(fksk::launch_builtin_rows_sched(P, waves, s.queue.as<uint32_t>(), s.qbase, lds, s.stream, a, rec));
+    if (trec) HIP_OK(fksk::launch_builtin_rows_time(s.fam_spec, P, waves, s.queue.as<uint32_t>(), s.qbase, lds, s.stream, a, trec));
+    else if (rec) HIP_OK(fksk::launch_builtin_rows_sched(P, waves, s.queue.as<uint32_t>(), s.qbase, lds, s.stream, a, rec));
     else if (profiled) HIP_OK(fksk::launch_builtin_rows_prof(kf, P, waves, s.queue.as<uint32_t>(), s.qbase, lds, s.stream, a));
     else HIP_OK(fksk::launch_builtin_rows(kf, P, waves, s.queue.as<uint32_t>(), s.qbase, lds, s.stream, a));
     s.qbase += (uint32_t)P + (uint32_t)waves * kRowsPerWave;   // every row makes one final, empty claim
@@ -1362,14 +1452,15 @@ class DeviceEngine {
   }
 
   void launch_rows_native(Slot& s, int P, size_t fn_bytes, const int64_t* kc_dev, bool profiled = false,
-                          SchedRec* rec = nullptr) {
+                          SchedRec* rec = nullptr, TimeRec* trec = nullptr) {
     // the two-wave kernel for every batch (its heap top follows the programs in
     // flight); four programs per wave only on request (native_rows = 4)
-    // (rec: a schedule launch runs the two-wave schedule instance, whatever `native_duo` / `native_rows` say)
-    const int ra = rec ? 1 : native_rows_opt_ > 0 ? native_rows_opt_ : (native_duo_ || P <= 2 * num_cus_ ? 1 : kRowsPerWave);
+    // (rec: a schedule launch runs the two-wave schedule instance, whatever `native_duo` / `native_rows` say;
+    // trec: a time launch the two-wave time instance)
+    const int ra = rec || trec ? 1 : native_rows_opt_ > 0 ? native_rows_opt_ : (native_duo_ || P <= 2 * num_cus_ ? 1 : kRowsPerWave);
     DevWorkload Wl = W_;
     const int entries = row_heap_entries(W_.n_pods);
-    if (ra == 1 && (native_duo_ || rec)) {
+    if (ra == 1 && (native_duo_ || rec || trec)) {
       // two waves per program (heap wave + scoring wave, replay_duo.hip.h)
       const int T = duo_top(std::max(P, native_inflight_));
       Wl.heap_top = T;
@@ -1388,8 +1479,10 @@ class DeviceEngine {
       if (std::getenv("FKS_DEBUG_LAUNCH"))
         std::fprintf(stderr, "[fks] native duo: P=%d T=%d lds=%zu per_cu=%d stream=%p\n", P, T, lds,
                      last_duo_per_cu_, (void*)s.stream);
-      HIP_OK(rec ? fksk::launch_native_duo_sched(P, lds, s.stream, a, nat, rec)
-                 : fksk::launch_native_duo(P, lds, s.stream, a, nat));
+      if (trec) last_time_instance_ = "duo_native";
+      HIP_OK(trec  ? fksk::launch_native_duo_time(P, lds, s.stream, a, nat, trec)
+             : rec ? fksk::launch_native_duo_sched(P, lds, s.stream, a, nat, rec)
+                   : fksk::launch_native_duo(P, lds, s.stream, a, nat));
       last_native_rows_ = 0;   // 0: the two-wave kernel
       last_native_waves_ = 2 * P;
       return;
@@ -1488,6 +1581,8 @@ class DeviceEngine {
   int64_t budget_ = 0;
   uint32_t max_events_ = 0;
   size_t sched_cap_ = size_t(256) << 20;   // `schedule_bytes`: record bytes per slot
+  bool time_ok_ = true;                    // the workload passed the time-metrics overflow gate (`time_ok`)
+  std::string last_time_instance_;         // instance of the last time launch (info: time_instance_last)
   int heap_top_opt_ = -1;
   bool partial_delmap_off_ = false;
   bool wave_duo_ = false;   // NPASS-4 builtin launches on the two-wave kernel (`wave_duo`)

@@ -185,6 +185,21 @@ hipError_t launch_native_duo_sched(int P, size_t lds, hipStream_t stream, const 
                                    const fksd::RowNativeArgs& nat, fksd::SchedRec* rec);
 int native_duo_sched_blocks_per_cu(size_t lds);
 
+// Time-metrics mode: separate instances that carry one fksd::TimeRec of
+// lane-resident accumulators through the replay and write it to trec[p]
+// (device_common.h).  Tables of their own: the composite and the mixed-family
+// row kernel (fam: FAM_COMPOSITE_LINEAR or anything else), the mixed-family
+// HBM-heap one-wave kernel per NPASS, the two-wave native kernel and the
+// HBM-heap one-wave native kernel per NPASS.  trec is a trailing kernel parameter.
+hipError_t launch_builtin_time(int npass, int P, size_t lds, hipStream_t s, const BuiltinArgs& a, fksd::TimeRec* trec);
+hipError_t launch_builtin_rows_time(int fam, int P, int waves, uint32_t* queue, uint32_t qbase, size_t lds, hipStream_t s,
+                                    const BuiltinArgs& a, fksd::TimeRec* trec);
+int rows_time_waves_per_cu(int fam, size_t lds);
+hipError_t launch_native_time(int npass, int P, size_t lds, hipStream_t s, const NativeArgs& a, fksd::TimeRec* trec);
+hipError_t launch_native_duo_time(int P, size_t lds, hipStream_t stream, const BuiltinArgs& a,
+                                  const fksd::RowNativeArgs& nat, fksd::TimeRec* trec);
+int native_duo_time_blocks_per_cu(size_t lds);
+
 // addresses of the native programs' runtime library (fks_rt_binop, fks_rt_unop, register floor)
 hipError_t native_rt_table(uint64_t* dev_out, hipStream_t s);
 // glibc_math.h on the device (tests): fn 0 exp, 1 log, 2 pow; n arguments, one per lane

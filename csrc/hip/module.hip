@@ -831,6 +831,9 @@ PYBIND11_MODULE(_fks_hip, m) {
       .def("submit_native_schedule", &DeviceEngine::submit_native_schedule)
       .def("wait_schedule", &DeviceEngine::wait_schedule)
       .def("schedule_chunk", &DeviceEngine::schedule_chunk)
+      .def("submit_builtin_time", &DeviceEngine::submit_builtin_time)
+      .def("submit_native_time", &DeviceEngine::submit_native_time)
+      .def("wait_time", &DeviceEngine::wait_time)
       .def("native_rt_table", &DeviceEngine::native_rt_table);
   py::class_<DeviceSuite>(m, "DeviceSuite")
       .def(py::init<py::list, int>(), py::arg("engines"), py::arg("n_slots") = 4)

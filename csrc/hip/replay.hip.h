@@ -581,11 +581,13 @@ struct WaveNodes {
 // (comments at each say why), held to them by the device tests alone.
 // Sched = SchedSink (schedule-mode instances): every commit also stores the
 // pod's record (device_common.h SchedRec); NoSched adds nothing.
-template <int NPASS, class Scorer, class Prof = NoProf, bool FLAT = false, class Sched = NoSched>
+// Time = TimeSink (time-metrics instances): every commit also feeds the wave's
+// lane-resident TimeAcc, written to the policy's TimeRec at the end; NoTime adds nothing.
+template <int NPASS, class Scorer, class Prof = NoProf, bool FLAT = false, class Sched = NoSched, class Time = NoTime>
 __device__ void replay_one(const DevWorkload& W, const DevWorkload* Wcold, Scorer& scorer, FKS_GLOBAL uint64_t* hbuf,
                            FKS_LDS uint64_t* htop, int T, FKS_LDS uint32_t* delmap, FKS_LDS int32_t* inv,
                            DevResult* out,
-                           uint64_t* prof_out = nullptr, Sched sched = Sched{}) {
+                           uint64_t* prof_out = nullptr, Sched sched = Sched{}, Time tsink = Time{}) {
   // W: the kernel-argument copy (hot fields, kept in SGPRs); Wcold: the same
   // struct in global memory (cold_ptr).
   // hbuf: the policy's heap array -- LDS (fast, 2 policies/CU on the 8k trace)
@@ -615,6 +617,8 @@ __device__ void replay_one(const DevWorkload& W, const DevWorkload* Wcold, Score
   WaveNodes<NPASS> ns{lane, nr, wcnt};
   ns.init(W);
   int64_t n_repush = 0, n_dropped = 0;
+  TimeAcc<false> tacc;   // (Time::kOn only)
+  if constexpr (Time::kOn) tacc.init();
   int n = N;
   __syncthreads();
   prof.start();
@@ -787,6 +791,11 @@ __device__ void replay_one(const DevWorkload& W, const DevWorkload* Wcold, Score
         if constexpr (Sched::kOn) {
           if (lane == 0) sched_put(sched.rec + rank, t, best_node, gmask);
         }
+        if constexpr (Time::kOn) {
+          // a fresh creation's event time is the pod's creation time: only a retry has waited
+          const int64_t wait = kind == kRetry ? t - (int64_t)W.pod_ctime[rank] : 0;
+          tacc.commit(lane, wait, (int64_t)dt, pod.cpu, pod.mem, pod.ngpu, pod.gmilli, pod.dur);
+        }
         prof.mark(PH_COMMIT);
       }
     }
@@ -802,6 +811,7 @@ __device__ void replay_one(const DevWorkload& W, const DevWorkload* Wcold, Score
   }
   if (prof_out) prof.flush(prof_out);
   ns.write(out, n_repush, n_dropped);
+  if constexpr (Time::kOn) tacc.write(tsink.rec, lane, ns.exc == EXC_NONE);
 }
 
 }  // namespace fksd

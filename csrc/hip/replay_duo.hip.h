@@ -228,10 +228,12 @@ __device__ void pop_reinsert64(const RowHeap& hp, int n, uint64_t last, int j, u
 // machine code they had before the functions existed.
 // SCHED (schedule-mode instance): the scoring wave also stores every placed
 // pod's record into sched[p * n_pods + rank] (device_common.h SchedRec).
-template <bool PROF = false, bool SCHED = false>
+// TIME (time-metrics instance): the scoring wave carries the TimeAcc of its
+// 16 lanes and writes trec[p] with the result (device_common.h TimeRec).
+template <bool PROF = false, bool SCHED = false, bool TIME = false>
 __device__ void replay_duo(const DevWorkload& W, const DevWorkload* Wdev, uint64_t* gheap, DevResult* out,
                            RowNativeArgs nat, double* table, uint64_t* prof_out = nullptr, int slot = -1,
-                           int hslot = -1, SchedRec* sched = nullptr) {
+                           int hslot = -1, SchedRec* sched = nullptr, TimeRec* trec = nullptr) {
   uint64_t pacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   uint64_t plast = 0;
   auto mark = [&](int ph) {
@@ -489,6 +491,8 @@ __device__ void replay_duo(const DevWorkload& W, const DevWorkload* Wdev, uint64
     }
   };
   uint32_t k = 0;
+  TimeAcc<true> tacc;   // (TIME instance only)
+  if constexpr (TIME) tacc.init();
   if constexpr (PROF) plast = __builtin_amdgcn_s_memtime();
   for (;;) {
     asm volatile("" : "+v"(jv));
@@ -627,6 +631,11 @@ __device__ void replay_duo(const DevWorkload& W, const DevWorkload* Wdev, uint64
         if constexpr (SCHED) {
           if (jv == best_node) sched_put(sched + (size_t)p * N + rank, t, best_node, gmask);
         }
+        if constexpr (TIME) {
+          // a fresh creation's event time is the pod's creation time: only a retry has waited
+          const int64_t wait = kind == kRetry ? t - (int64_t)*global_ptr(&W.pod_ctime[rank]) : 0;
+          tacc.commit(jv, wait, (int64_t)dt, pod.cpu, pod.mem, pod.ngpu, pod.gmilli, pod.dur);
+        }
         if (jv == best_node) {
           nr.cpu_left[0] -= pod.cpu;
           nr.mem_left[0] -= pod.mem;
@@ -742,6 +751,7 @@ __device__ void replay_duo(const DevWorkload& W, const DevWorkload* Wdev, uint64
     if (!ok && jv != 10) v = 0.0;
     if (jv < 13) table[(size_t)p * 13 + jv] = v;
   }
+  if constexpr (TIME) tacc.write(trec + p, jv, exc == EXC_NONE);
 }
 
 }  // namespace fksd

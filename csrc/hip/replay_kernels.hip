@@ -201,6 +201,19 @@ __global__ FKS_FAM_BOUNDS(true, -1, NPASS) void k_replay_builtin_sched(fksk::Bui
 }
 constexpr std::array<Row<fksk::BuiltinArgs, SchedRec*>, 1> kBuiltinSched = {
     {{0, k_replay_builtin_sched<FKS_NPASS>}}};
+// Time-metrics mode: the mixed-family, HBM-heap instance that also carries the
+// policy's TimeAcc and writes trec[p] (a trailing parameter, as above).
+template <int NPASS>
+__global__ FKS_FAM_BOUNDS(true, -1, NPASS) void k_replay_builtin_time(fksk::BuiltinArgs a, TimeRec* trec) {
+  const int p = blockIdx.x;
+  const Slot s = policy_slot<true>(a.W, a.gheap, p);
+  BuiltinScorerDev<-1> sc;
+  load_policy<-1>(sc, a, p);
+  replay_one<NPASS, BuiltinScorerDev<-1>, NoProf, FKS_WAVE_FLAT != 0, NoSched, TimeSink>(
+      a.W, kernarg_workload(), sc, s.h, s.top, s.T, s.delmap, s.inv, a.out + p, nullptr, NoSched{}, TimeSink{trec + p});
+}
+constexpr std::array<Row<fksk::BuiltinArgs, TimeRec*>, 1> kBuiltinTime = {
+    {{0, k_replay_builtin_time<FKS_NPASS>}}};
 #endif
 
 #if FKS_KIND == 0 && FKS_NPASS == 4
@@ -323,6 +336,23 @@ __global__ __launch_bounds__(64, 2) void k_replay_rows_sched(fksk::BuiltinArgs a
 }
 constexpr std::array<Row<fksk::BuiltinArgs, int, uint32_t*, uint32_t, SchedRec*>, 1> kRowsSched = {
     {{0, k_replay_rows_sched}}};
+// Time-metrics mode: every row carries its policy's TimeAcc and writes trec[p].
+// The composite instance at the waves per SIMD of k_replay_rows_c5 (the default
+// launch's composite instance), the mixed one as k_replay_rows<-1>.
+#ifndef FKS_ROW_TIME_WAVES
+#define FKS_ROW_TIME_WAVES 5
+#endif
+template <int FAM>
+__global__ __launch_bounds__(64, FAM < 0 ? 2 : FKS_ROW_TIME_WAVES) void k_replay_rows_time(fksk::BuiltinArgs a, int P,
+                                                                                         uint32_t* queue, uint32_t qbase,
+                                                                                         TimeRec* trec) {
+  replay_rows<FAM, RowNoProf, FKS_ROW_FLAT != 0, false, true>(a.W, kernarg_workload(), a.fam, a.weights, a.gheap, a.out, P,
+                                                               queue, qbase, nullptr,
+                                                               RowNativeArgs{nullptr, nullptr, nullptr}, kRowsPerWave,
+                                                               a.table, nullptr, trec);
+}
+constexpr std::array<Row<fksk::BuiltinArgs, int, uint32_t*, uint32_t, TimeRec*>, 2> kRowsTime = {
+    {{FAM_COMPOSITE_LINEAR, k_replay_rows_time<FAM_COMPOSITE_LINEAR>}, {-1, k_replay_rows_time<-1>}}};
 using RowsRow = Row<fksk::BuiltinArgs, int, uint32_t*, uint32_t>;
 template <int... F>
 constexpr std::array<RowsRow, sizeof...(F) + 2> rows_rows(Keys<F...>) {
@@ -406,6 +436,10 @@ __global__ __launch_bounds__(128, 1) void k_replay_native_duo_prof(fksk::Builtin
 // Schedule mode: the scoring wave also stores every placed pod's record (rec: [P, n_pods])
 __global__ __launch_bounds__(128, 1) void k_replay_native_duo_sched(fksk::BuiltinArgs a, RowNativeArgs nat, SchedRec* rec) {
   replay_duo<false, true>(a.W, kernarg_workload(), a.gheap, a.out, nat, a.table, nullptr, -1, -1, rec);
+}
+// Time-metrics mode: the scoring wave carries the program's TimeAcc and writes trec[p]
+__global__ __launch_bounds__(128, 1) void k_replay_native_duo_time(fksk::BuiltinArgs a, RowNativeArgs nat, TimeRec* trec) {
+  replay_duo<false, false, true>(a.W, kernarg_workload(), a.gheap, a.out, nat, a.table, nullptr, -1, -1, nullptr, trec);
 }
 // ----------------------------------------------------------------------------
 // The resident program service: a resident pool of two-wave workgroups that replays
@@ -616,6 +650,25 @@ __global__ __launch_bounds__(64, 2) void k_replay_native_sched(fksk::NativeArgs 
 }
 constexpr std::array<Row<fksk::NativeArgs, SchedRec*>, 1> kNativeSched = {
     {{0, k_replay_native_sched<FKS_NPASS>}}};
+// Time-metrics mode: the HBM-heap instance that also carries the program's TimeAcc and writes trec[p]
+template <int NPASS>
+__global__ __launch_bounds__(64, 2) void k_replay_native_time(fksk::NativeArgs a, TimeRec* trec) {
+  const int p = blockIdx.x;
+  const Slot s = policy_slot<true>(a.W, a.gheap, p);
+  NativeScorerDev sc;
+  sc.fn = prog_of(uniu64(a.fn[p]));
+  sc.feas = prog_feas(uniu64(a.fn[p]));
+  sc.gmem = a.W.gmem_total;
+  const FKS_GLOBAL int64_t* ksrc = global_ptr(a.kc + a.koff[p]);   // as k_replay_native
+  FKS_LDS int64_t* kl = reinterpret_cast<FKS_LDS int64_t*>(lds_ptr(s.vregs));
+  for (int i = lane_id(); i < kKcLds; i += kWave) kl[i] = ksrc[i];
+  sc.kc = kl;
+  replay_one<NPASS, NativeScorerDev, NoProf, false, NoSched, TimeSink>(a.W, kernarg_workload(), sc, s.h, s.top, s.T,
+                                                                      s.delmap, s.inv, a.out + p, nullptr, NoSched{},
+                                                                      TimeSink{trec + p});
+}
+constexpr std::array<Row<fksk::NativeArgs, TimeRec*>, 1> kNativeTime = {
+    {{0, k_replay_native_time<FKS_NPASS>}}};
 template <int... G>
 constexpr std::array<Row<fksk::NativeArgs>, sizeof...(G)> native_rows(Keys<G...>) {
   return {{{G, k_replay_native<FKS_NPASS, G != 0>}...}};
@@ -629,6 +682,8 @@ constexpr std::array<Row<fksk::BuiltinArgs, RowNativeArgs>, 2> kNativeDuo = {
     {{0, k_replay_native_duo}, {1, k_replay_native_duo_prof}}};
 constexpr std::array<Row<fksk::BuiltinArgs, RowNativeArgs, SchedRec*>, 1> kNativeDuoSched = {
     {{0, k_replay_native_duo_sched}}};
+constexpr std::array<Row<fksk::BuiltinArgs, RowNativeArgs, TimeRec*>, 1> kNativeDuoTime = {
+    {{0, k_replay_native_duo_time}}};
 constexpr std::array<Row<fksk::ServiceArgs>, 1> kService = {{{0, k_native_service}}};
 constexpr std::array<Row<fksk::SuiteArgs, RowNativeArgs>, 1> kNativeDuoSuite = {{{0, k_replay_native_duo_suite}}};
 #endif
@@ -646,6 +701,8 @@ template <int NPASS> hipError_t unit_launch_vm(bool gheap, int P, size_t lds, hi
 template <int NPASS> hipError_t unit_launch_native(bool gheap, int P, size_t lds, hipStream_t s, const NativeArgs& a);
 template <int NPASS> hipError_t unit_launch_builtin_sched(int P, size_t lds, hipStream_t s, const BuiltinArgs& a, SchedRec* rec);
 template <int NPASS> hipError_t unit_launch_native_sched(int P, size_t lds, hipStream_t s, const NativeArgs& a, SchedRec* rec);
+template <int NPASS> hipError_t unit_launch_builtin_time(int P, size_t lds, hipStream_t s, const BuiltinArgs& a, TimeRec* trec);
+template <int NPASS> hipError_t unit_launch_native_time(int P, size_t lds, hipStream_t s, const NativeArgs& a, TimeRec* trec);
 
 #if FKS_KIND == 0
 template <>
@@ -662,8 +719,12 @@ hipError_t unit_launch_builtin_sched<FKS_NPASS>(int P, size_t lds, hipStream_t s
   return launch_row(kBuiltinSched, 0, dim3(P), dim3(64), lds, s, a, rec);
 }
 template <>
+hipError_t unit_launch_builtin_time<FKS_NPASS>(int P, size_t lds, hipStream_t s, const BuiltinArgs& a, TimeRec* trec) {
+  return launch_row(kBuiltinTime, 0, dim3(P), dim3(64), lds, s, a, trec);
+}
+template <>
 hipError_t unit_attrs<0, FKS_NPASS>(int mx) {
-  hipError_t e = raise_lds(mx, kBuiltinHbm, kBuiltinLds, kBuiltinSched);
+  hipError_t e = raise_lds(mx, kBuiltinHbm, kBuiltinLds, kBuiltinSched, kBuiltinTime);
 #if FKS_NPASS == 4
   if (e == hipSuccess) e = raise_lds(mx, kBuiltinDuo);
 #endif
@@ -712,8 +773,13 @@ hipError_t launch_builtin_rows_sched(int P, int waves, uint32_t* queue, uint32_t
   return launch_row(kRowsSched, 0, dim3(waves), dim3(64), lds, st, a, P, queue, qbase, rec);
 }
 int rows_sched_waves_per_cu(size_t lds) { return blocks_per_cu(kRowsSched, 0, 64, lds); }
+hipError_t launch_builtin_rows_time(int fam, int P, int waves, uint32_t* queue, uint32_t qbase, size_t lds, hipStream_t st,
+                                    const BuiltinArgs& a, TimeRec* trec) {
+  return launch_row(kRowsTime, fam, dim3(waves), dim3(64), lds, st, a, P, queue, qbase, trec);
+}
+int rows_time_waves_per_cu(int fam, size_t lds) { return blocks_per_cu(kRowsTime, fam, 64, lds); }
 template <>
-hipError_t unit_attrs<3, 1>(int mx) { return raise_lds(mx, kRowsProf, kRows, kRowsSched); }
+hipError_t unit_attrs<3, 1>(int mx) { return raise_lds(mx, kRowsProf, kRows, kRowsSched, kRowsTime); }
 #endif
 
 
@@ -726,7 +792,16 @@ template <>
 hipError_t unit_launch_native_sched<FKS_NPASS>(int P, size_t lds, hipStream_t s, const NativeArgs& a, SchedRec* rec) {
   return launch_row(kNativeSched, 0, dim3(P), dim3(64), lds, s, a, rec);
 }
+template <>
+hipError_t unit_launch_native_time<FKS_NPASS>(int P, size_t lds, hipStream_t s, const NativeArgs& a, TimeRec* trec) {
+  return launch_row(kNativeTime, 0, dim3(P), dim3(64), lds, s, a, trec);
+}
 #if FKS_NPASS == 1
+hipError_t launch_native_duo_time(int P, size_t lds, hipStream_t st, const BuiltinArgs& a, const fksd::RowNativeArgs& nat,
+                                  TimeRec* trec) {
+  return launch_row(kNativeDuoTime, 0, dim3(P), dim3(128), lds, st, a, nat, trec);
+}
+int native_duo_time_blocks_per_cu(size_t lds) { return blocks_per_cu(kNativeDuoTime, 0, 128, lds); }
 hipError_t launch_native_duo_sched(int P, size_t lds, hipStream_t st, const BuiltinArgs& a, const fksd::RowNativeArgs& nat,
                                    SchedRec* rec) {
   return launch_row(kNativeDuoSched, 0, dim3(P), dim3(128), lds, st, a, nat, rec);
@@ -762,9 +837,9 @@ hipError_t launch_gm_batch(int fn, const double* x, const double* y, double* out
 #endif
 template <>
 hipError_t unit_attrs<4, FKS_NPASS>(int mx) {
-  hipError_t e = raise_lds(mx, kNative, kNativeSched);
+  hipError_t e = raise_lds(mx, kNative, kNativeSched, kNativeTime);
 #if FKS_NPASS == 1
-  if (e == hipSuccess) e = raise_lds(mx, kRowsNative, kNativeDuo, kNativeDuoSched, kNativeDuoSuite);
+  if (e == hipSuccess) e = raise_lds(mx, kRowsNative, kNativeDuo, kNativeDuoSched, kNativeDuoTime, kNativeDuoSuite);
   // (the service kernel's static LDS -- the claim word -- counts against the 160 KiB too)
   if (e == hipSuccess) e = raise_lds(mx - 64, kService);
 #endif
@@ -800,6 +875,12 @@ hipError_t launch_builtin_sched(int npass, int P, size_t lds, hipStream_t s, con
 }
 hipError_t launch_native_sched(int npass, int P, size_t lds, hipStream_t s, const NativeArgs& a, SchedRec* rec) {
   return for_npass(npass, [&](auto n) { return unit_launch_native_sched<decltype(n)::value>(P, lds, s, a, rec); });
+}
+hipError_t launch_builtin_time(int npass, int P, size_t lds, hipStream_t s, const BuiltinArgs& a, TimeRec* trec) {
+  return for_npass(npass, [&](auto n) { return unit_launch_builtin_time<decltype(n)::value>(P, lds, s, a, trec); });
+}
+hipError_t launch_native_time(int npass, int P, size_t lds, hipStream_t s, const NativeArgs& a, TimeRec* trec) {
+  return for_npass(npass, [&](auto n) { return unit_launch_native_time<decltype(n)::value>(P, lds, s, a, trec); });
 }
 hipError_t set_all_attrs(int max_lds) {
   for (auto unit : {unit_attrs<0, 1>, unit_attrs<0, 2>, unit_attrs<0, 4>, unit_attrs<1, 1>, unit_attrs<1, 2>,

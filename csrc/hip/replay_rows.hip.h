@@ -719,11 +719,14 @@ __device__ __forceinline__ void write_row_result(const RowAcc& acc, int jv, int 
 // wave (the whole heap in LDS, no other row's divergence in the event loop).
 // SCHED (schedule-mode instance): every commit also stores the pod's record
 // into sched[p * n_pods + rank] (device_common.h SchedRec).
-template <int FAM, class Prof = RowNoProf, bool FLAT = FKS_ROW_FLAT != 0, bool SCHED = false>
+// TIME (time-metrics instance): every commit also feeds the row's lane-resident
+// TimeAcc, written to trec[p] with the result (device_common.h TimeRec).
+template <int FAM, class Prof = RowNoProf, bool FLAT = FKS_ROW_FLAT != 0, bool SCHED = false, bool TIME = false>
 __device__ void replay_rows(const DevWorkload& W, const DevWorkload* Wdev, const int32_t* fam, const double* weights,
                             uint64_t* gheap, DevResult* out, int P, uint32_t* queue, uint32_t qbase,
                             uint64_t* prof_out = nullptr, RowNativeArgs nat = RowNativeArgs{nullptr, nullptr, nullptr},
-                            int rows_active = kRowsPerWave, double* table = nullptr, SchedRec* sched = nullptr) {
+                            int rows_active = kRowsPerWave, double* table = nullptr, SchedRec* sched = nullptr,
+                            TimeRec* trec = nullptr) {
   constexpr bool kNative = FAM == kFamNative;
   const int ra = kNative ? rows_active : kRowsPerWave;
   // W: the kernel-argument copy, read once for the hot scalars below; every
@@ -795,6 +798,7 @@ __device__ void replay_rows(const DevWorkload& W, const DevWorkload* Wdev, const
   uint32_t wcp[kRowClassSlots / 2];
   auto wcount = [&](int sl) -> uint32_t { return (wcp[sl >> 1] >> (16 * (sl & 1))) & 0xFFFFu; };
   RowAcc acc;
+  TimeAcc<true> tacc;   // (TIME instances only)
   int32_t processed = 0, next_fire = INT32_MAX;
   int n = 0;
   FKS_LDS uint64_t* rcs = heap.top + (T + 1);   // [0] trace hash, [1] threshold bits
@@ -853,6 +857,7 @@ __device__ void replay_rows(const DevWorkload& W, const DevWorkload* Wdev, const
 #pragma unroll
     for (int k = 0; k < kRowClassSlots / 2; ++k) wcp[k] = 0u;
     acc.init();   // (drops the fragmentation stash too: an aborted replay leaves its own behind)
+    if constexpr (TIME) tacc.init();
     processed = 0;
     rcn[0] = 0u; rcn[1] = 0u; rcn[2] = 0u;
     const double thr = Wb->thr_after_fire;
@@ -1045,6 +1050,11 @@ __device__ void replay_rows(const DevWorkload& W, const DevWorkload* Wdev, const
           if constexpr (SCHED) {
             if (jv == best_node) sched_put(sched + (size_t)p * N + rank, t, best_node, gmask);
           }
+          if constexpr (TIME) {
+            // a fresh creation's event time is the pod's creation time: only a retry has waited
+            const int64_t wait = kind == kRetry ? t - (int64_t)*global_ptr(&W.pod_ctime[rank]) : 0;
+            tacc.commit(jv, wait, (int64_t)dt, pod.cpu, pod.mem, pod.ngpu, pod.gmilli, pod.dur);
+          }
           ecat = 2;
           prof.mark(PH_COMMIT);
         }
@@ -1100,6 +1110,7 @@ __device__ void replay_rows(const DevWorkload& W, const DevWorkload* Wdev, const
     // ---------------- replay done (or aborted): result, then the next policy
     write_row_result(acc, jv, rbase, processed, exc, (int64_t)rcn[0], (int)rcn[1], rcs[0], out + p,
                      table ? table + (size_t)p * 13 : nullptr);
+    if constexpr (TIME) tacc.write(trec + p, jv, exc == EXC_NONE);
     p = claim();
     have = p < P;
     if (have) begin();

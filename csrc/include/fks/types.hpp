@@ -9,6 +9,8 @@
 #include <string>
 #include <vector>
 
+#include "time_rec.hpp"
+
 namespace fks {
 
 // Exception classes a policy replay can end with.  They mirror the Python
@@ -55,6 +57,7 @@ struct SimOptions {
   int64_t budget = 0;            // VM instruction budget per priority evaluation (0 = unlimited)
   bool record_values = false;    // keep snapshot / frag values (exact fallback, tests)
   bool record_placements = false;
+  bool record_time = false;      // fill SimResult::time at every commit (time_rec.hpp)
   int64_t check_invariants = 0;  // verify resource accounting every K events and at the end (0 = off)
   bool record_states = false;    // per creation event: pod + node/GPU state + decision (screening data)
 };
@@ -73,6 +76,7 @@ struct SimResult {
   std::vector<int32_t> placement;    // node per pod (-1 never placed; record_placements)
   std::vector<uint8_t> placement_gpus;    // the pod's GPUs on that node, bit j = GPU j (record_placements)
   std::vector<int64_t> placement_start;   // time of the creation event that placed it (-1 never placed)
+  TimeRec time;                           // record_time
   // record_states: per creation event, [pod, chosen node (-1 failed), cpu_left[N],
   // mem_left[N], gpu_left[N], gmilli_left[G]]
   std::vector<int32_t> states;

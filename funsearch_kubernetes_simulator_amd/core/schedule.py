@@ -45,6 +45,73 @@ def _running(keys: np.ndarray, delta: np.ndarray) -> np.ndarray:
     return out
 
 
+def _time_record_ints(node: np.ndarray, start: np.ndarray, workload: Workload) -> np.ndarray:
+    """One schedule's record with Python ints throughout (any magnitude short of the record's 64 bits)."""
+    from .time_metrics import RECORD_WORDS, wait_bucket
+    p = workload.pods
+    slots = [0] * 8
+    hist = [0] * 32
+    for i in np.flatnonzero(node >= 0):
+        t, dur = int(start[i]), int(p.pod_dur[i])
+        wait = t - int(p.pod_ctime[i])
+        ngpu = int(p.pod_ngpu[i])
+        slots[0] += wait
+        slots[1] = max(slots[1], wait)
+        slots[2] = max(slots[2], t + dur)
+        slots[3] += int(p.pod_cpu[i]) * dur
+        slots[4] += int(p.pod_mem[i]) * dur
+        slots[5] += ngpu * dur
+        slots[6] += ngpu * int(p.pod_gmilli[i]) * dur
+        slots[7] += 1
+        hist[wait_bucket(wait)] += 1
+    rec = np.zeros(RECORD_WORDS, dtype=np.int64)
+    rec[:8] = slots
+    rec[8:] = np.array(hist, dtype=np.uint32).view(np.int64)
+    return rec
+
+
+def _time_records(node: np.ndarray, start: np.ndarray, workload: Workload, chunk: int = 128) -> np.ndarray:
+    """Time-metrics records [P, 24] int64 of schedules `node`, `start` [P, n_pods]
+    (`core.time_metrics`), from the schedules and the workload alone.  int64
+    numpy sums where Python ints show that none can overflow (every term is
+    >= 0 for a valid schedule, so the sums over all pods bound them), else
+    Python ints pod by pod."""
+    from .time_metrics import RECORD_WORDS
+    p = workload.pods
+    P, n = node.shape
+    rec = np.zeros((P, RECORD_WORDS), dtype=np.int64)
+    if P == 0 or n == 0:
+        return rec
+    dur = p.pod_dur.astype(np.int64)
+    ctime = p.pod_ctime.astype(np.int64)
+    ngpu = p.pod_ngpu.astype(np.int64)
+    cols = (p.pod_cpu.astype(np.int64), p.pod_mem.astype(np.int64), ngpu, ngpu * p.pod_gmilli.astype(np.int64))
+    t_hi = max(int(start.max()), 0)
+    bound = max([n * t_hi + sum(int(d) for d in dur)] + [sum(abs(int(x)) * abs(int(d)) for x, d in zip(c, dur)) for c in cols])
+    if bound >= 2 ** 62 or int(min(c.min() for c in cols + (dur,))) < 0:
+        for i in range(P):
+            rec[i] = _time_record_ints(node[i], start[i], workload)
+        return rec
+    prods = [c * dur for c in cols]
+    edges = np.int64(1) << np.arange(63, dtype=np.int64)   # bit_length(w) = edges <= w, counted
+    for lo in range(0, P, chunk):
+        placed = node[lo:lo + chunk] >= 0
+        st = start[lo:lo + chunk].astype(np.int64)
+        wait = np.where(placed, st - ctime, 0)
+        rec[lo:lo + chunk, 0] = wait.sum(axis=1)
+        rec[lo:lo + chunk, 1] = wait.max(axis=1)
+        rec[lo:lo + chunk, 2] = np.where(placed, st + dur, 0).max(axis=1)
+        for k, pr in enumerate(prods):
+            rec[lo:lo + chunk, 3 + k] = np.where(placed, pr, 0).sum(axis=1)
+        rec[lo:lo + chunk, 7] = placed.sum(axis=1)
+        bucket = np.minimum(np.searchsorted(edges, wait.ravel(), side="right"), 31).reshape(wait.shape)
+        bucket = np.where(placed, bucket, 32)   # (a pod never placed: counted nowhere)
+        hist = np.zeros((len(placed), 33), dtype=np.int64)
+        np.add.at(hist, (np.arange(len(placed))[:, None], bucket), 1)
+        rec[lo:lo + chunk, 8:] = hist[:, :32].astype(np.uint32).view(np.int64)
+    return rec
+
+
 @dataclass
 class Schedule:
     """One policy's schedule, in trace pod order."""
@@ -69,6 +136,18 @@ class Schedule:
         """Start minus original creation time per pod (trace seconds; -1 for a pod never placed)."""
         w = self.start - workload.pods.pod_ctime.astype(np.int64)
         return np.where(self.node >= 0, w, -1)
+
+    def time_record(self, workload: Workload) -> np.ndarray:
+        """The schedule's time-metrics record (`core.time_metrics`: 24 int64
+        words) from the schedule and the workload alone -- plain numpy and
+        Python ints, no engine."""
+        return _time_records(self.node[None], self.start[None], workload)[0]
+
+    def time_metrics(self, workload: Workload):
+        """`TimeMetricsBatch` of this one schedule (all zero if its replay raised)."""
+        from .time_metrics import TimeMetricsBatch
+        return TimeMetricsBatch.from_records(np.asarray(self.row)[None], self.time_record(workload)[None],
+                                             self.engine, workload)
 
     def first_difference(self, other: "Schedule", workload: Optional[Workload] = None) -> Optional[int]:
         """Trace index of the first pod, in (start, rank) order, whose record
@@ -231,6 +310,13 @@ class ScheduleBatch:
     def __getitem__(self, i: int) -> Schedule:
         i = range(len(self))[i]
         return Schedule(self.node[i], self.gpu_mask[i], self.start[i], self.rows[i], self.engine[i], self.node_ids)
+
+    def time_metrics(self, workload: Workload):
+        """`TimeMetricsBatch` derived from the schedules and the workload alone
+        (no engine): the reference every engine's time mode is held to."""
+        from .time_metrics import TimeMetricsBatch
+        rec = _time_records(self.node, self.start, workload)
+        return TimeMetricsBatch.from_records(self.rows, rec, list(self.engine), workload)
 
     @classmethod
     def empty(cls, n: int, n_pods: int, node_ids=None) -> "ScheduleBatch":

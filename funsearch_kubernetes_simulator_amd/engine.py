@@ -172,6 +172,20 @@ def _object_schedule_worker(args):
     return object_engine_schedule(code, workload, budget_s)
 
 
+def object_engine_time(code: str, workload: Workload, budget_s: float = 0.0):
+    """The object engine's time metrics, derived from what its replay left on
+    the pods (`object_engine_schedule`, then `Schedule.time_record`): (row
+    [13], record [24] int64).  All zero if the replay raised."""
+    from .core.schedule import Schedule
+    row, node, mask, start = object_engine_schedule(code, workload, budget_s)
+    return row, Schedule(node, mask, start, row, "object").time_record(workload)
+
+
+def _object_time_worker(args):
+    code, workload, budget_s = args
+    return object_engine_time(code, workload, budget_s)
+
+
 def _exc_code(exc: BaseException) -> int:
     if isinstance(exc, ReplayTimeout):
         return int(Exc.BUDGET)
@@ -349,6 +363,82 @@ class Evaluator:
                     results = [_object_schedule_worker(j) for j in jobs]
                 for i, (row, node, mask, start) in zip(rest, results):
                     out.put([i], ScheduleBatch(node[None], mask[None], start[None], row[None], ["object"]))
+                    self._bump("object", 1)
+            else:
+                for i in rest:
+                    out.rows[i, COLS["exc"]] = int(Exc.UNSUPPORTED)
+                    out.engine[i] = "none"
+        return out
+
+    # -- time metrics: waits, makespan, busy time (core/time_metrics.py) -------------------
+    def time_family(self, family, weights: np.ndarray):
+        """`TimeMetricsBatch` of a family batch (`family`: one name, or one per
+        row): the rows of `evaluate_family` and each replay's time record."""
+        if self.device is not None:
+            return self.device.time_builtin(family, weights)
+        from .ops import cpu_engine
+        self._time_gate()
+        return cpu_engine.time_builtin_batch(self.workload, family, weights,
+                                             cpu_engine.SimOptions(**self._cpu_opts()), self.cpu_threads)
+
+    def _time_gate(self) -> None:
+        """Time mode refuses a workload on which one of its 64-bit sums could overflow."""
+        from .core.time_metrics import overflow_gate
+        from .ops.hip_engine import UnsupportedWorkload
+        if not hasattr(self, "_time_gate_reason"):
+            self._time_gate_reason = overflow_gate(self.workload, self.device.layout["time_bits"]
+                                                   if self.device is not None else None)
+        if self._time_gate_reason:
+            raise UnsupportedWorkload(f"time mode: {self._time_gate_reason} (a 64-bit sum could overflow)")
+
+    def time_programs(self, codes: Sequence[str]):
+        """`TimeMetricsBatch` of program texts, routed as `schedule_programs`
+        routes them: the device's native time kernels, then -- for programs the
+        JIT declines and rows it defers -- the CPU VM, then the object engine.
+        `engine[i]` says where record i came from; a program that raises has
+        its `exc` in its row and an all-zero record."""
+        from .core.time_metrics import TimeMetricsBatch
+        from .ops import cpu_engine
+        self._time_gate()
+        codes = list(codes)
+        compiled = self.compile_batch(codes)
+        n = len(codes)
+        out = TimeMetricsBatch.empty(n, self.workload)
+        done = [False] * n
+        pending = [i for i, p in enumerate(compiled) if p is not None]
+        if self.device is not None and self.native:
+            exact = getattr(self.device, "math_exact", True)
+            dev_idx = [i for i in pending if compiled[i].device_ok and (exact or not compiled[i].uses_libm)]
+            if dev_idx:
+                got = self.device.time_native([compiled[i] for i in dev_idx])
+                for j, i in enumerate(dev_idx):
+                    if not _native_deferred(got.rows[j], self._bump):
+                        out.put([i], got, [j])
+                        done[i] = True
+                        self._bump("device_native", 1)
+        cpu_idx = [i for i in pending if not done[i]]
+        if cpu_idx:
+            got = cpu_engine.time_program_batch(self.workload, [compiled[i] for i in cpu_idx],
+                                                cpu_engine.SimOptions(**self._cpu_opts()), self.cpu_threads)
+            for j, i in enumerate(cpu_idx):
+                row = got.rows[j]
+                if int(row[COLS["exc"]]) in (Exc.UNSUPPORTED, Exc.BUDGET) or row[COLS["inexact"]]:
+                    continue
+                out.put([i], got, [j])
+                done[i] = True
+                self._bump("cpu_vm", 1)
+        rest = [i for i in range(n) if not done[i]]
+        if rest:
+            if self._object_engine_ok():
+                budget_s = float(self.options.get("object_timeout_s", 600.0))
+                jobs = [(codes[i], self.workload, budget_s) for i in rest]
+                if len(rest) > 1 and self.object_workers > 1:
+                    with ProcessPoolExecutor(max_workers=min(self.object_workers, len(rest))) as ex:
+                        results = list(ex.map(_object_time_worker, jobs))
+                else:
+                    results = [_object_time_worker(j) for j in jobs]
+                for i, (row, rec) in zip(rest, results):
+                    out.put([i], TimeMetricsBatch.from_records(row[None], rec[None], "object", self.workload))
                     self._bump("object", 1)
             else:
                 for i in rest:
@@ -969,6 +1059,13 @@ def schedule(codes, device="auto", workload: Optional[Workload] = None, **option
     each pod's node, GPUs and start time under every program, beside its row."""
     codes = [codes] if isinstance(codes, str) else list(codes)
     return Evaluator(workload, device, options).schedule_programs(codes)
+
+
+def time_metrics(codes, device="auto", workload: Optional[Workload] = None, **options):
+    """`TimeMetricsBatch` of policy programs (one program text or a list of
+    them): waits, makespan and busy time of every program's replay, beside its row."""
+    codes = [codes] if isinstance(codes, str) else list(codes)
+    return Evaluator(workload, device, options).time_programs(codes)
 
 
 def copy_workload(w: Workload) -> Workload:

@@ -160,6 +160,31 @@ def schedule_program_batch(w: Workload, progs: Sequence[CompiledPolicy], options
     return _schedule_batch(w, out, "cpu")
 
 
+# ---------------------------------------------------------------------------- time metrics
+def time_builtin_batch(w: Workload, family, weights: np.ndarray, options: Optional[SimOptions] = None,
+                       threads: int = 0):
+    """`TimeMetricsBatch` of built-in family members (`family`: one name or one
+    per row of `weights`): the oracle fills the record at each commit
+    (csrc/cpu/engine.hpp record_time_metrics), beside the rows
+    `simulate_builtin_batch` returns."""
+    from ..core.time_metrics import TimeMetricsBatch
+    weights = np.ascontiguousarray(weights, dtype=np.float64)
+    weights = weights.reshape(len(weights), -1)
+    rows, rec = native().time_builtin_batch(native_workload(w), _family_ids(family, len(weights)), weights,
+                                            (options or SimOptions()).as_dict(), threads or default_threads())
+    return TimeMetricsBatch.from_records(rows, rec, "cpu", w)
+
+
+def time_program_batch(w: Workload, progs: Sequence[CompiledPolicy], options: Optional[SimOptions] = None,
+                       threads: int = 0):
+    """`TimeMetricsBatch` of compiled programs on the CPU VM (rows as `simulate_program_batch`)."""
+    from ..core.time_metrics import TimeMetricsBatch
+    rows, rec = native().time_program_batch(native_workload(w), [p.code for p in progs], [p.fconst for p in progs],
+                                            [p.iconst for p in progs], [p.ctag for p in progs],
+                                            (options or SimOptions()).as_dict(), threads or default_threads())
+    return TimeMetricsBatch.from_records(rows, rec, "cpu", w)
+
+
 # ---------------------------------------------------------------------------- native programs on the CPU
 _host_libs: dict = {}
 

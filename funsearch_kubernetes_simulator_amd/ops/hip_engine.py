@@ -217,7 +217,11 @@ def prepare_device_workload(w: Workload, snapshot_interval: float = 0.05) -> Dic
         used_gmilli=int((c.gpu_milli_total.astype(np.int64) - c.gpu_milli_left).sum()),
     )
     fire, thr_after = snapshot_schedule(P, snapshot_interval)
+    # time-metrics mode (core/time_metrics.py): can a 64-bit sum overflow on this workload?
+    from ..core.time_metrics import overflow_gate
+    time_gate = overflow_gate(w, time_bits)
     return dict(
+        time_ok=time_gate is None, time_gate=time_gate or "",
         snap_fire=fire, thr_after_fire=float(thr_after),
         n_nodes=N, n_pods=P, n_classes=int(classes.size), npass=npass,
         cpu_total=pad(c.node_cpu_total, np.int32), cpu_left=pad(c.node_cpu_left, np.int32),
@@ -272,6 +276,7 @@ class DeviceEvaluator:
         self._native_mods: Dict[int, tuple] = {}   # slot -> JIT modules its batch in flight calls into
         self._sched_jobs: Dict[int, dict] = {}     # slot -> schedule batch in flight (its chunks, `wait_schedule`)
         self._sched_order: Optional[np.ndarray] = None
+        self._time_jobs: Dict[int, dict] = {}      # slot -> time-metrics batch in flight (`wait_time`)
         #: the resident program service (start_service): slot -> (P, native rows, first ring index)
         self._svc: Optional[dict] = None
         self._svc_post: Dict[int, Tuple[int, np.ndarray, int, np.ndarray]] = {}   # slot -> (P, rows, first, data slots)
@@ -575,6 +580,74 @@ class DeviceEvaluator:
             return ScheduleBatch.empty(0, self.workload.pods.n_pods, list(self.workload.cluster.node_ids))
         self.submit_schedule_native(0, progs)
         return self.wait_schedule(0)
+
+    # -- time metrics: waits, makespan and busy time per replay (core/time_metrics.py) ---------
+    # A time launch runs the time instances of the replay kernels
+    # (csrc/hip/launch.h): lane-resident integer accumulators fed at each
+    # commit, one 192-byte record per policy beside the usual row.
+    def _time_gate(self) -> None:
+        if not self.layout["time_ok"]:
+            raise UnsupportedWorkload(f"time mode: {self.layout['time_gate']} (a 64-bit sum could overflow)")
+
+    def submit_time_builtin(self, slot: int, family: "str | Sequence[str]", weights: Optional[np.ndarray] = None,
+                            n: Optional[int] = None) -> None:
+        """Start a family time-metrics batch on `slot`; `wait_time(slot)` collects it."""
+        self._time_gate()
+        fam, W = self._builtin_args(family, weights, n)
+        self._eng.submit_builtin_time(slot, fam, W)
+        self._time_jobs[slot] = dict(kind="builtin")
+
+    def submit_time_native(self, slot: int, progs: Sequence[CompiledPolicy], batch=None) -> None:
+        """Start a program time-metrics batch on `slot` (a kernel launch of its
+        own, also while the program service runs).  Programs the native backend
+        declines come back as EXC_UNSUPPORTED rows with all-zero records."""
+        self._time_gate()
+        if batch is None:
+            batch = self.prepare_native(progs)
+        idx = np.flatnonzero(batch.ok)
+        job = dict(kind="native", batch=batch, idx=idx, total=len(progs))
+        try:
+            if idx.size:
+                self._eng.submit_native_time(slot, batch.fn[idx], batch.kc, batch.koff[idx])
+        except BaseException:
+            self.native_compiler.release(batch.modules)
+            raise
+        self._time_jobs[slot] = job
+
+    def wait_time(self, slot: int):
+        """The `TimeMetricsBatch` of the time batch in flight on `slot`."""
+        from ..core.time_metrics import TimeMetricsBatch
+        job = self._time_jobs.pop(slot)
+        if job["kind"] == "builtin":
+            rows, rec = self._eng.wait_time(slot)
+            return TimeMetricsBatch.from_records(rows, rec, "hip", self.workload)
+        try:
+            got = None
+            if job["idx"].size:
+                rows, rec = self._eng.wait_time(slot)
+                got = TimeMetricsBatch.from_records(rows, rec, "hip-native", self.workload)
+        finally:
+            self.native_compiler.release(job["batch"].modules)
+        out = TimeMetricsBatch.empty(job["total"], self.workload)
+        out.rows[:, 10] = 100.0   # EXC_UNSUPPORTED: not native -> the caller's next engine
+        if got is not None:
+            out.put(job["idx"], got)
+        return out
+
+    def time_builtin(self, family: "str | Sequence[str]", weights: Optional[np.ndarray] = None,
+                     n: Optional[int] = None):
+        """`TimeMetricsBatch` of a family batch: the rows `evaluate_builtin`
+        returns and each replay's time record."""
+        self.submit_time_builtin(0, family, weights, n)
+        return self.wait_time(0)
+
+    def time_native(self, progs: Sequence[CompiledPolicy]):
+        """`TimeMetricsBatch` of natively compiled programs (rows as `evaluate_native`)."""
+        from ..core.time_metrics import TimeMetricsBatch
+        if not progs:
+            return TimeMetricsBatch.empty(0, self.workload)
+        self.submit_time_native(0, progs)
+        return self.wait_time(0)
 
     # -- asynchronous slots: several batches in flight on separate HIP streams --------------
     @property
